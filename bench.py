@@ -2,6 +2,13 @@
 """bench.py — device-resident CRC-32 FCS throughput on 1518-B frames (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-gpu F] [--len L]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warmup steps, times K steps, writes the last step's CRCs if
+--dump-outputs is given, and prints the contract fields (`roofline` then holds only the timed steps'
+own HIP-event figure; `verified`, `cpu_baseline` and `configs` are null). Everything else below is
+measured only with --full. The input frames are a fixed counter-based byte stream, so with the same
+arguments two builds can be compared CRC for CRC through --dump-outputs.
 
 --gpus N is authoritative: started without a launcher (no WORLD_SIZE), bench.py starts the N ranks
 itself under torch.distributed.run before any GPU call; under a launcher WORLD_SIZE must equal N
@@ -14,7 +21,8 @@ embarrassingly (each rank owns a contiguous slice of the global frame stream), s
 collectives are the timing barrier and the max-over-ranks of the elapsed time — none on the
 data path. value = bytes of all ranks / max rank time, in GiB/s.
 
-Printed (rank 0, one JSON line): the contract fields plus
+Printed (rank 0, one JSON line): the contract fields plus, with --full,
+  verified     — a zlib spot check of sampled frames of the last step's CRCs;
   roofline     — the FCS kernel's achieved algorithmic GB/s (frame bytes per launch / average
                  launch time from HIP events on the launch stream) against the 8 TB/s HBM peak;
                  `traffic` = HBM bytes per launch from the committed rocprofv3 PMC summary
@@ -183,6 +191,28 @@ def _spot(crcs, frame_bytes, idx):
     """Number of sampled frames whose GPU CRC differs from zlib.crc32 (= ether_fcs)."""
     import zlib
     return sum(int(zlib.crc32(frame_bytes(int(i))) != int(crcs[int(i)])) for i in idx)
+
+
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs: all files of a run together stay under this
+DUMP_SAMPLE = 2 << 20       # frames sampled per run when the CRCs of all frames would exceed the cap
+
+
+def dump_outputs(path: str, out, rank: int, world: int) -> str:
+    """--dump-outputs: what the timed path's last step returned to its caller, the per-frame CRCs of
+    this rank, as float64 (every u32 exact) in DIR/fcs.npy (DIR/fcs_rank<r>.npy at N > 1). Above the
+    cap a fixed sample: frame 0, the last frame and seeded draws, in ascending frame order, the same
+    frames every run."""
+    import numpy as np
+    crcs = out.cpu().numpy().view(np.uint32)
+    n = len(crcs)
+    if n * 8 * world > DUMP_CAP_BYTES:
+        k = max(1, DUMP_SAMPLE // world)
+        rng = np.random.default_rng(SEED + rank)
+        crcs = crcs[np.unique(np.concatenate([rng.integers(0, n, k), [0, n - 1]]))]
+    os.makedirs(path, exist_ok=True)
+    name = os.path.join(path, "fcs.npy" if world == 1 else f"fcs_rank{rank}.npy")
+    np.save(name, crcs.astype(np.float64))
+    return name
 
 
 def extra_configs(torch, na, dev, stream, reps=5, host_gib=4.0):
@@ -666,6 +696,12 @@ def main():
                     help="N > 1: IMIX frames per GPU of the sharded configs[2] run (0 = skip)")
     ap.add_argument("--host-gib-per-gpu", type=float, default=4.0,
                     help="N > 1: GiB of pinned host frames per rank for the host-inclusive run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the measured read ceilings, the committed profile figures, the "
+                         "zlib spot check, the CPU baseline and the other configs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the CRCs of the last step (a fixed, seeded sample of them "
+                         "when they exceed the size cap) to DIR/fcs.npy (DIR/fcs_rank<r>.npy at N > 1) as float64")
     args = ap.parse_args()
 
     # --gpus is authoritative: no launcher -> start the ranks here, before any
@@ -720,33 +756,20 @@ def main():
     arena = torch.empty(nbytes + 64, dtype=torch.uint8, device=dev)
     na.fill_splitmix_dev(arena, nbytes, SEED, lo * L, stream)
     out = torch.empty(n, dtype=torch.int32, device=dev)
-    sink = torch.zeros(4, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
 
     def step():
         na.fixed_dev(arena, L, L, n, out, stream)
 
-    # ---- read-stream ceiling over the same buffer: untimed calibration, also warms the memory
-    #      system and clocks before the warmup steps ----
-    rs = torch.cuda.Event(enable_timing=True)
-    re_ = torch.cuda.Event(enable_timing=True)
-    na.read_stream_dev(arena, nbytes, sink, stream)
-    rs.record(stream)
-    for _ in range(5):
-        na.read_stream_dev(arena, nbytes, sink, stream)
-    re_.record(stream)
-    torch.cuda.synchronize()
-    read_ms = rs.elapsed_time(re_) / 5
-    read_gbs = nbytes / (read_ms * 1e-3) / 1e9
-    # the LDS-DMA read ceiling: the headline kernel's own loads and schedule without the CRC work
-    na.dma_stream_dev(arena, nbytes, sink, stream)
-    rs.record(stream)
-    for _ in range(5):
-        na.dma_stream_dev(arena, nbytes, sink, stream)
-    re_.record(stream)
-    torch.cuda.synchronize()
-    dma_gbs = nbytes / (rs.elapsed_time(re_) / 5 * 1e-3) / 1e9
-
+    read_gbs = dma_gbs = None
+    if args.full:
+        # ---- read-stream ceiling over the same buffer: untimed calibration before the warmup steps ----
+        sink = torch.zeros(4, dtype=torch.int32, device=dev)
+        read_ms = _time_launches(lambda: na.read_stream_dev(arena, nbytes, sink, stream), 5, stream, torch)
+        read_gbs = nbytes / (read_ms * 1e-3) / 1e9
+        # the LDS-DMA read ceiling: the headline kernel's own loads and schedule without the CRC work
+        dma_ms = _time_launches(lambda: na.dma_stream_dev(arena, nbytes, sink, stream), 5, stream, torch)
+        dma_gbs = nbytes / (dma_ms * 1e-3) / 1e9
 
     for _ in range(args.warmup):
         step()
@@ -777,10 +800,13 @@ def main():
     total_bytes = total * L
     value = total_bytes * args.steps / tmax / GIB
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
     # ---- spot check of this rank's output: sampled frames re-created on the host, checked with
     #      zlib.crc32 (the stdlib CRC-32 = ether_fcs; the oracle is only for the CPU-baseline leg) ----
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         import zlib
         crcs = out.cpu().numpy().view(np.uint32)
         rng = np.random.default_rng(rank)
@@ -795,24 +821,31 @@ def main():
         verified = int(flag.item()) == 0
 
     achieved_gbs = nbytes / (kernel_ms * 1e-3) / 1e9
-    pmc = _load_pmc_traffic(n, L, "fcs_dma_kernel")
+    # a plain run: the timed steps' own HIP-event figure only; --full adds the committed PMC traffic
+    # and trace figures and the two read ceilings measured above
     roofline = {"bound": "hbm", "achieved": round(achieved_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
-                "traffic": pmc[0] if pmc else None,
-                "traffic_source": pmc[1] if pmc else None,
+                "traffic": None,
+                "traffic_source": None,
                 "algorithmic_bytes_per_launch": nbytes,
-                "kernel_ms_per_launch": round(kernel_ms, 4),
-                "read_stream_gbs": round(read_gbs, 1),
-                "frac_of_read_stream": round(achieved_gbs / read_gbs, 4),
-                "dma_stream_gbs": round(dma_gbs, 1),
-                "frac_of_dma_stream": round(achieved_gbs / dma_gbs, 4)}
-    prof = _load_kernel_profile("void fcs::fcs_dma_kernel<2, false>", nbytes) if L == 1518 and F == 64 << 20 else None
-    if prof:   # the committed trace of this command (another box, under the tracer): box spread in DESIGN §4.2
-        roofline.update(prof)
+                "kernel_ms_per_launch": round(kernel_ms, 4)}
+    if args.full:
+        pmc = _load_pmc_traffic(n, L, "fcs_dma_kernel")
+        roofline.update({"traffic": pmc[0] if pmc else None,
+                         "traffic_source": pmc[1] if pmc else None,
+                         "read_stream_gbs": round(read_gbs, 1),
+                         "frac_of_read_stream": round(achieved_gbs / read_gbs, 4),
+                         "dma_stream_gbs": round(dma_gbs, 1),
+                         "frac_of_dma_stream": round(achieved_gbs / dma_gbs, 4)})
+        prof = _load_kernel_profile("void fcs::fcs_dma_kernel<2, false>", nbytes) if L == 1518 and F == 64 << 20 else None
+        if prof:   # the committed trace of this command (another box, under the tracer): box spread in DESIGN §4.2
+            roofline.update(prof)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline()
+    if not args.full:   # the other configs below are --full's
+        args.no_configs = True
     configs = None
     if world == 1 and not args.no_configs and F == 64 << 20 and L == 1518:
         del arena, out
@@ -858,6 +891,7 @@ def main():
                        "parallelism": f"frames sharded over {world} GPU(s), no collective on the data path",
                        "devices": devices, "distinct_devices": distinct},
             "pct_hbm_peak": round(100.0 * value * GIB / 1e9 / world / HBM_PEAK_GBS, 2),
+            "full": args.full,
             "verified": verified,
             "roofline": roofline,
             "cpu_baseline": cpu,

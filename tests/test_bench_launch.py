@@ -62,6 +62,28 @@ def test_single_gpu_default_needs_no_launcher():
     assert rec["n_gpus"] == 1 and len(rec["config"]["devices"]) == 1
 
 
+def test_dump_outputs_whole_when_small_and_a_fixed_sample_above_the_cap(tmp_path):
+    """--dump-outputs: every CRC as float64 (exact for any u32) while they fit the cap; above it the
+    same seeded frames every run, first and last frame included, all files of a run within the cap."""
+    import numpy as np
+    import torch
+    small = torch.tensor([0, 1, -1, -(2**31), 2**31 - 1], dtype=torch.int32)
+    a = np.load(bench.dump_outputs(str(tmp_path / "s"), small, 0, 1))
+    assert a.dtype == np.float64
+    assert a.tolist() == [0.0, 1.0, 2.0**32 - 1, 2.0**31, 2.0**31 - 1]
+    n = bench.DUMP_CAP_BYTES // 8 + 1
+    big = torch.arange(n, dtype=torch.int32)
+    p = bench.dump_outputs(str(tmp_path / "b"), big, 0, 1)
+    assert os.path.basename(p) == "fcs.npy"
+    b = np.load(p)
+    assert b.dtype == np.float64 and 1 << 20 < len(b) <= bench.DUMP_SAMPLE + 2
+    assert b[0] == 0 and b[-1] == n - 1 and np.all(np.diff(b) > 0)
+    assert np.array_equal(b, np.load(bench.dump_outputs(str(tmp_path / "b2"), big, 0, 1)))
+    sizes = [os.path.getsize(bench.dump_outputs(str(tmp_path / "r"), big, r, 8)) for r in range(8)]
+    assert sorted(os.listdir(tmp_path / "r")) == [f"fcs_rank{r}.npy" for r in range(8)]
+    assert sum(sizes) <= bench.DUMP_CAP_BYTES
+
+
 def test_label_devices_marks_shared_gpus():
     e = [{"rank": 0, "pci": "0000:05:00"}, {"rank": 1, "pci": "0000:05:00"}, {"rank": 2, "pci": "0000:15:00"}]
     devs, distinct = bench.label_devices(e)

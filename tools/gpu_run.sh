@@ -5,7 +5,7 @@
 # step ends the call (no GPU step runs after a failure, a fault or a time limit). Steps:
 #   suite                 the whole GPU suite (pytest -m gpu) and the graft smoke
 #   tests:PATH[,PATH]     the named test files only
-#   bench[:ARGS]          python bench.py ARGS (default: the driver's plain line) -> OUT/bench.json
+#   bench[:ARGS]          python bench.py ARGS (default: --full, every figure of the line) -> OUT/bench.json
 #   ranks2                the 2-rank bench rehearsal on one GPU (bench.py --gpus 2, self-launched)
 #   profile[:TAG]         tools/profile_round.sh OUT/prof TAG (trace, PMC traffic, the bundle under
 #                         OUT/prof/bundle, then the plain line quoting it, rehearsals)
@@ -32,10 +32,11 @@ for step in "$@"; do
       timeout -k 10 900 python -u -m pytest ${arg//,/ } -x -v --timeout 300 --timeout-method thread > "$log" 2>&1; rc=$?
       echo "tests rc=$rc"; grep -E "passed|failed|error" "$log" | tail -3 ;;
     bench)
+      arg=${arg:---full}
       timeout -k 10 600 python -u bench.py ${arg//,/ } > "$out/$n-bench.json" 2> "$log"; rc=$?
       echo "bench rc=$rc"; tail -c 1500 "$out/$n-bench.json" ;;
     ranks2)
-      timeout -k 10 600 python -u bench.py --gpus 2 --frames-per-gpu 16777216 --imix-frames-per-gpu 33554432 \
+      timeout -k 10 600 python -u bench.py --gpus 2 --full --frames-per-gpu 16777216 --imix-frames-per-gpu 33554432 \
         > "$out/$n-ranks2.json" 2> "$log"; rc=$?
       echo "ranks2 rc=$rc"; tail -c 1500 "$out/$n-ranks2.json" ;;
     profile)

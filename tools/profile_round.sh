@@ -24,7 +24,7 @@ step() {   # tag, timeout, command...
   return 0
 }
 line() { grep '^{"metric"' "$1" | tail -1; }
-step bench_under_rocprof 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 bench.py
+step bench_under_rocprof 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 bench.py --full
 line "$OUT/bench_under_rocprof.log" > "$B/${TAG}_bench_line_under_rocprof.json"
 step pmc_fetch 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o run --pmc FETCH_SIZE -- python3 tools/prof_fixed.py --reps 3
 step pmc_write 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/pmc_write" -o run --pmc WRITE_SIZE -- python3 tools/prof_fixed.py --reps 3
@@ -43,11 +43,11 @@ step traffic_jumbo 60 python3 tools/traffic_summary.py "$OUT" "$B/${TAG}_pmc_tra
   --frames 16777216 --len 9000 --sub-fetch jumbo_fetch --sub-write jumbo_write
 mkdir -p "profiles/$TAG" && cp "$B"/* "profiles/$TAG/"
 # the plain line, quoting the bundle just written
-step bench_plain 400 python3 bench.py
+step bench_plain 400 python3 bench.py --full
 line "$OUT/bench_plain.log" > "$B/${TAG}_bench_line.json"
-step rehearsal_2ranks 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --frames-per-gpu 16777216 --imix-frames-per-gpu 33554432 --host-gib-per-gpu 2 --steps 5 --warmup 2
+step rehearsal_2ranks 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --frames-per-gpu 16777216 --imix-frames-per-gpu 33554432 --host-gib-per-gpu 2 --steps 5 --warmup 2
 line "$OUT/rehearsal_2ranks.log" > "$B/${TAG}_bench_2ranks_on_1gpu_rehearsal.json"
-step rehearsal_8ranks 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --frames-per-gpu 4194304 --imix-frames-per-gpu 8388608 --host-gib-per-gpu 0.5 --steps 5 --warmup 2
+step rehearsal_8ranks 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --full --frames-per-gpu 4194304 --imix-frames-per-gpu 8388608 --host-gib-per-gpu 0.5 --steps 5 --warmup 2
 line "$OUT/rehearsal_8ranks.log" > "$B/${TAG}_bench_8ranks_on_1gpu_rehearsal.json"
 echo "bundle: $(ls "$B" | tr '\n' ' ')"
 exit 0

@@ -9,6 +9,12 @@ SAN=${SAN:-thread}
 HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(dirname "$(dirname "$HERE")")
 OUT=${TMPDIR:-/tmp}/txq_san_${SAN//,/_}
+# ThreadSanitizer's fixed shadow layout refuses to start ("unexpected memory mapping") on hosts whose
+# address-space randomisation is wider than it expects (vm.mmap_rnd_bits 32): run its programs with
+# randomisation off for that process alone, where setarch may do that
+if [ "$SAN" = thread ] && setarch "$(uname -m)" -R true 2> /dev/null; then
+  timeout() { command timeout "${@:1:3}" setarch "$(uname -m)" -R "${@:4}"; }
+fi
 g++ -std=c++17 -O1 -g -fsanitize="$SAN" -fno-sanitize-recover=all -DFCS_TXQ_TSAN -I"$ROOT/include" \
     "$HERE/txq_stress.cpp" "$HERE/gpu_stub.cpp" "$ROOT/nstack_amd/csrc/fcs_txq.cpp" \
     "$ROOT/nstack_amd/csrc/fcs_host_crc.cpp" -o "$OUT" -lpthread
