@@ -17,7 +17,11 @@ LIB_PATH = os.environ.get("NSTACK_FCS_LIB") or os.path.join(_HERE, "libnstack_fc
 
 __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fixed_host",
            "batch_host", "tx_host", "tx_batch_host", "host_buffer", "host_free", "verify_dev", "verify_fixed_dev", "verify_host", "fill_splitmix_dev", "read_stream_dev", "timed_fixed_dev",
-           "tables_blob", "TxQueue", "RxQueue", "set_var_threshold", "pcap_scan", "pcap_read", "pcap_write", "inet_batch_dev", "inet_fixed_dev", "inet_batch_host", "inet_set_flat_threshold", "inet_set_dma_threshold", "ip_checksum", "tcp_checksum", "udp_checksum", "INET_MODES", "engine_init", "engine_fini", "version", "LIB_PATH", "EXPORTS", "engine_stats", "shard_plan", "dma_stream_dev", "stream_load_dev", "load_faults", "FAULTS_PATH"]
+           "tables_blob", "TxQueue", "RxQueue", "set_var_threshold", "pcap_scan", "pcap_read", "pcap_write", "inet_batch_dev", "inet_fixed_dev", "inet_batch_host", "inet_set_flat_threshold", "inet_set_dma_threshold", "ip_checksum", "tcp_checksum", "udp_checksum", "INET_MODES", "engine_init", "engine_fini", "version", "LIB_PATH", "EXPORTS", "engine_stats", "shard_plan", "dma_stream_dev", "stream_load_dev", "load_faults", "FAULTS_PATH",
+           "rx_validate_dev", "rx_validate_fixed_dev", "rx_validate_host", "rx_validate_set_dma_threshold", "rxv_route",
+           "rxv_last_launch", "RXV_EXPORTS", "RXV_F_TRAILER", "RXV_FCS_BAD",
+           "RXV_RUNT", "RXV_IPV4", "RXV_IP_BAD_HDR", "RXV_IP_BAD_LEN", "RXV_IP_BAD_CSUM", "RXV_FRAG", "RXV_L4_CHECKED",
+           "RXV_L4_BAD_CSUM", "RXV_L4_SHORT", "RXV_PROTO_SHIFT"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -40,6 +44,14 @@ EXPORTS = [
     "fcs_rxq_create", "fcs_rxq_receive", "fcs_rxq_stats", "fcs_rxq_fallbacks", "fcs_rxq_set_host_max",
     "fcs_rxq_small_batches", "fcs_rxq_destroy",
 ]
+
+# include/nstack_rxv.h — one-pass RX validation (its own list: EXPORTS mirrors the five older headers)
+RXV_EXPORTS = ["ether_rx_validate_dev", "ether_rx_validate_fixed_dev", "ether_rx_validate_host",
+               "ether_rx_validate_set_dma_threshold", "fcs_debug_rxv_route", "fcs_debug_rxv_last_launch"]
+RXV_F_TRAILER = 1
+RXV_FCS_BAD, RXV_RUNT, RXV_IPV4, RXV_IP_BAD_HDR, RXV_IP_BAD_LEN = 0x001, 0x002, 0x004, 0x008, 0x010
+RXV_IP_BAD_CSUM, RXV_FRAG, RXV_L4_CHECKED, RXV_L4_BAD_CSUM, RXV_L4_SHORT = 0x020, 0x040, 0x080, 0x100, 0x200
+RXV_PROTO_SHIFT = 16
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -171,6 +183,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "inet_ip_checksum": (c.c_uint16, [vp, c.c_size_t]),
         "inet_tcp_checksum": (c.c_uint16, [u32, u32, vp, c.c_size_t]),
         "inet_udp_checksum": (c.c_uint16, [vp, c.c_size_t, u32, u32]),
+        "ether_rx_validate_dev": (i32, [vp, u64, vp, vp, u32, u32, vp, vp, u64, vp]),
+        "ether_rx_validate_fixed_dev": (i32, [vp, u64, u32, u64, u32, u32, vp, vp, vp]),
+        "ether_rx_validate_host": (c.c_int64, [vp, u64, vp, vp, u32, u32, vp, u64]),
+        "ether_rx_validate_set_dma_threshold": (u64, [u64]),
+        "fcs_debug_rxv_route": (i32, [u64, u64, u32, u64, c.c_char_p, u64]),
+        "fcs_debug_rxv_last_launch": (i32, [c.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -601,3 +619,54 @@ def udp_checksum(data, src: int, dst: int) -> int:
     """udp_checksum(buff, len, src, dst) of src/udp.c:136-174 (raw in_addr_t values)."""
     b = bytes(data)
     return load().inet_udp_checksum(b, len(b), src, dst)
+
+
+# ---- one-pass RX validation (include/nstack_rxv.h) ----
+def _u32(x: int, what: str) -> int:
+    if not 0 <= int(x) <= 0xFFFFFFFF:
+        raise ValueError(f"{what} {x!r} is not a uint32")
+    return int(x)
+
+
+def rx_validate_dev(arena, arena_bytes: int, off, length, verdict, n: int, flags: int = RXV_F_TRAILER,
+                    bad_mask: int = 0, bad=None, stream=None) -> None:
+    """verdict[i] (u32) = the RXV_* word of arena[off[i]:off[i]+len[i]]; *bad (u64, optional) = frames
+    with verdict & bad_mask. Device arrays; asynchronous on `stream`."""
+    _check(load().ether_rx_validate_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), _u32(flags, "flags"),
+                                        _u32(bad_mask, "bad_mask"), _ptr(verdict), _ptr(bad), n, _stream(stream)),
+           "ether_rx_validate_dev")
+
+
+def rx_validate_fixed_dev(base, stride: int, length: int, n: int, verdict, flags: int = RXV_F_TRAILER,
+                          bad_mask: int = 0, bad=None, stream=None) -> None:
+    _check(load().ether_rx_validate_fixed_dev(_ptr(base), stride, length, n, _u32(flags, "flags"),
+                                              _u32(bad_mask, "bad_mask"), _ptr(verdict), _ptr(bad), _stream(stream)),
+           "ether_rx_validate_fixed_dev")
+
+
+def rx_validate_host(arena, arena_bytes: int, off, length, verdict, n: int, flags: int = RXV_F_TRAILER,
+                     bad_mask: int = 0) -> int:
+    """Host form: fills verdict[i] and returns the number of frames with verdict & bad_mask."""
+    return _check(load().ether_rx_validate_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length),
+                                                _u32(flags, "flags"), _u32(bad_mask, "bad_mask"), _ptr(verdict), n),
+                  "ether_rx_validate_host")
+
+
+def rx_validate_set_dma_threshold(frames: int) -> int:
+    """Fixed-stride batches of more than `frames` frames use the LDS-DMA kernel (when their geometry
+    fits its slots); returns the old value."""
+    return int(load().ether_rx_validate_set_dma_threshold(frames))
+
+
+def rxv_route(base: int, stride: int, length: int, n: int) -> str:
+    """The kernel a fixed-stride batch would take (fcs_debug_rxv_route; host arithmetic only)."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_rxv_route(base, stride, length, n, buf, 32), "fcs_debug_rxv_route")
+    return buf.value.decode()
+
+
+def rxv_last_launch() -> str:
+    """The kernel the last ether_rx_validate launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_rxv_last_launch(buf, 32), "fcs_debug_rxv_last_launch")
+    return buf.value.decode()

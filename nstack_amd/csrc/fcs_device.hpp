@@ -10,6 +10,11 @@ namespace fcs {
 __attribute__((visibility("hidden"))) int current_device(int *dev, int *cus);
 // The first device of the engine's device set (fcs_engine_init), for the host entry points.
 __attribute__((visibility("hidden"))) int engine_device0(int *dev, int *cus);
+// The constant table blob (fcs::kBlobWords words, fcs_tables.hpp) in device `dev`'s memory, for the
+// kernels of other translation units that stage the CRC tables (rxv_kernel.hip).
+__attribute__((visibility("hidden"))) int device_tables(int dev, const uint32_t **blob);
+// Bound of the register-load kernels' front-masking loop for fixed frames of `len` bytes (KParams::zmax).
+__attribute__((visibility("hidden"))) uint32_t mask_bound(uint32_t len);
 // memcpy into pinned staging, split over a few threads for large spans (host pipelines).
 __attribute__((visibility("hidden"))) void staging_copy(uint8_t *dst, const uint8_t *src, uint64_t bytes);
 // Asynchronous RX residue check over frames in fcs_host_alloc memory (the small-batch kernel reading

@@ -1587,6 +1587,16 @@ int fcs::current_device(int *dev, int *cus) {
     return 0;
 }
 
+uint32_t fcs::mask_bound(uint32_t len) { return ::mask_bound(len); }
+
+int fcs::device_tables(int dev, const uint32_t **blob) {
+    DevState *ds = nullptr;
+    const int rc = dev_state(dev, &ds);
+    if (rc) return rc;
+    *blob = ds->d_blob;
+    return 0;
+}
+
 int fcs::launch_with_counter(int dev, void *stream, const std::function<int(unsigned long long *)> &launch) {
     hipStream_t st = (hipStream_t)stream;
     DevState *ds = nullptr;
