@@ -47,9 +47,11 @@ def rxv_golden():
 
 @pytest.fixture(params=["general", "dma"], autouse=True)
 def rxv_kernel(request):
-    """Every test runs through both kernels (identical verdicts required): general = a quarter-wave per
-    frame with register loads (DMA threshold 1 << 63), dma = fixed-stride batches whose geometry fits
-    the LDS-DMA kernel's slots through it (threshold 0), everything else through the general kernel."""
+    """Every test runs under both DMA thresholds (identical verdicts required): general = 1 << 63, a
+    quarter-wave per frame with register loads for every batch; dma = 0, fixed-stride batches whose
+    geometry fits the LDS-DMA kernel's slots through rxv_dma_kernel. Variable and host batches always
+    take the general kernel (rxv::route), so in this file only test_fixed_form's in-band shapes reach
+    rxv_dma_kernel; tests/test_gpu_rxv_cuts.py holds the rest of that kernel's tests."""
     old = na.rx_validate_set_dma_threshold(0 if request.param == "dma" else (1 << 63))
     yield request.param
     na.rx_validate_set_dma_threshold(old)
