@@ -21,7 +21,11 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "rx_validate_dev", "rx_validate_fixed_dev", "rx_validate_host", "rx_validate_set_dma_threshold", "rxv_route",
            "rxv_last_launch", "RXV_EXPORTS", "RXV_F_TRAILER", "RXV_FCS_BAD",
            "RXV_RUNT", "RXV_IPV4", "RXV_IP_BAD_HDR", "RXV_IP_BAD_LEN", "RXV_IP_BAD_CSUM", "RXV_FRAG", "RXV_L4_CHECKED",
-           "RXV_L4_BAD_CSUM", "RXV_L4_SHORT", "RXV_PROTO_SHIFT"]
+           "RXV_L4_BAD_CSUM", "RXV_L4_SHORT", "RXV_PROTO_SHIFT",
+           "tx_seal_dev", "tx_seal_fixed_dev", "tx_seal_host", "tx_seal_set_dma_threshold", "txs_route",
+           "txs_last_launch", "TXS_EXPORTS", "TXS_FIELDS_DTYPE", "TXS_F_FCS", "TXS_F_UDP_ZERO", "TXS_FCS_SET", "TXS_RUNT",
+           "TXS_IPV4", "TXS_IP_BAD_HDR", "TXS_IP_BAD_LEN", "TXS_IP_CSUM_SET", "TXS_FRAG", "TXS_L4_CSUM_SET",
+           "TXS_L4_SHORT", "TXS_PROTO_SHIFT"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -52,6 +56,16 @@ RXV_F_TRAILER = 1
 RXV_FCS_BAD, RXV_RUNT, RXV_IPV4, RXV_IP_BAD_HDR, RXV_IP_BAD_LEN = 0x001, 0x002, 0x004, 0x008, 0x010
 RXV_IP_BAD_CSUM, RXV_FRAG, RXV_L4_CHECKED, RXV_L4_BAD_CSUM, RXV_L4_SHORT = 0x020, 0x040, 0x080, 0x100, 0x200
 RXV_PROTO_SHIFT = 16
+
+# include/nstack_txs.h — one-pass TX sealing (its own list, as RXV_EXPORTS)
+TXS_EXPORTS = ["ether_tx_seal_dev", "ether_tx_seal_fixed_dev", "ether_tx_seal_host",
+               "ether_tx_seal_set_dma_threshold", "fcs_debug_txs_route", "fcs_debug_txs_last_launch"]
+TXS_F_FCS, TXS_F_UDP_ZERO = 1, 2
+TXS_FCS_SET, TXS_RUNT, TXS_IPV4, TXS_IP_BAD_HDR, TXS_IP_BAD_LEN = 0x001, 0x002, 0x004, 0x008, 0x010
+TXS_IP_CSUM_SET, TXS_FRAG, TXS_L4_CSUM_SET, TXS_L4_SHORT = 0x020, 0x040, 0x080, 0x200
+TXS_PROTO_SHIFT = 16
+# struct txs_fields as a numpy structured dtype (8 bytes per frame)
+TXS_FIELDS_DTYPE = [("ip_csum", "<u2"), ("l4_csum", "<u2"), ("fcs", "<u4")]
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -189,6 +203,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "ether_rx_validate_set_dma_threshold": (u64, [u64]),
         "fcs_debug_rxv_route": (i32, [u64, u64, u32, u64, c.c_char_p, u64]),
         "fcs_debug_rxv_last_launch": (i32, [c.c_char_p, u64]),
+        "ether_tx_seal_dev": (i32, [vp, u64, vp, vp, u32, u32, vp, vp, vp, u64, vp]),
+        "ether_tx_seal_fixed_dev": (i32, [vp, u64, u32, u64, u32, u32, vp, vp, vp, vp]),
+        "ether_tx_seal_host": (c.c_int64, [vp, u64, vp, vp, u32, u32, vp, u64]),
+        "ether_tx_seal_set_dma_threshold": (u64, [u64]),
+        "fcs_debug_txs_route": (i32, [u64, u64, u32, u64, u32, c.c_char_p, u64]),
+        "fcs_debug_txs_last_launch": (i32, [c.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -669,4 +689,53 @@ def rxv_last_launch() -> str:
     """The kernel the last ether_rx_validate launch of this process launched."""
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_rxv_last_launch(buf, 32), "fcs_debug_rxv_last_launch")
+    return buf.value.decode()
+
+
+# ---- one-pass TX sealing (include/nstack_txs.h) ----
+def tx_seal_dev(arena, arena_bytes: int, off, length, n: int, flags: int = TXS_F_FCS, count_mask: int = 0,
+                status=None, fields=None, count=None, stream=None) -> None:
+    """Seals arena[off[i]:off[i]+len[i]] in place (with TXS_F_FCS the FCS goes behind each frame);
+    status[i] (u32, optional) = the TXS_* word, fields[i] (8 bytes, optional) = what was written, *count
+    (u64, optional) = frames with status & count_mask. Device arrays; asynchronous on `stream`."""
+    _check(load().ether_tx_seal_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), _u32(flags, "flags"),
+                                    _u32(count_mask, "count_mask"), _ptr(status), _ptr(fields), _ptr(count), n,
+                                    _stream(stream)),
+           "ether_tx_seal_dev")
+
+
+def tx_seal_fixed_dev(base, stride: int, length: int, n: int, flags: int = TXS_F_FCS, count_mask: int = 0,
+                      status=None, fields=None, count=None, stream=None) -> None:
+    _check(load().ether_tx_seal_fixed_dev(_ptr(base), stride, length, n, _u32(flags, "flags"),
+                                          _u32(count_mask, "count_mask"), _ptr(status), _ptr(fields), _ptr(count),
+                                          _stream(stream)),
+           "ether_tx_seal_fixed_dev")
+
+
+def tx_seal_host(arena, arena_bytes: int, off, length, n: int, flags: int = TXS_F_FCS, count_mask: int = 0,
+                 status=None) -> int:
+    """Host form: seals the frames of a host arena in place, fills status[i] (optional) and returns the
+    number of frames with status & count_mask."""
+    return _check(load().ether_tx_seal_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), _u32(flags, "flags"),
+                                            _u32(count_mask, "count_mask"), _ptr(status), n),
+                  "ether_tx_seal_host")
+
+
+def tx_seal_set_dma_threshold(frames: int) -> int:
+    """Fixed-stride batches of more than `frames` frames use the LDS-DMA kernel (when their geometry
+    fits its slots); returns the old value."""
+    return int(load().ether_tx_seal_set_dma_threshold(frames))
+
+
+def txs_route(base: int, stride: int, length: int, n: int, flags: int = TXS_F_FCS) -> str:
+    """The kernel a fixed-stride batch would take (fcs_debug_txs_route; host arithmetic only)."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_txs_route(base, stride, length, n, _u32(flags, "flags"), buf, 32), "fcs_debug_txs_route")
+    return buf.value.decode()
+
+
+def txs_last_launch() -> str:
+    """The kernel the last ether_tx_seal launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_txs_last_launch(buf, 32), "fcs_debug_txs_last_launch")
     return buf.value.decode()
