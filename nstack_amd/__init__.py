@@ -25,7 +25,10 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "tx_seal_dev", "tx_seal_fixed_dev", "tx_seal_host", "tx_seal_set_dma_threshold", "txs_route",
            "txs_last_launch", "TXS_EXPORTS", "TXS_FIELDS_DTYPE", "TXS_F_FCS", "TXS_F_UDP_ZERO", "TXS_FCS_SET", "TXS_RUNT",
            "TXS_IPV4", "TXS_IP_BAD_HDR", "TXS_IP_BAD_LEN", "TXS_IP_CSUM_SET", "TXS_FRAG", "TXS_L4_CSUM_SET",
-           "TXS_L4_SHORT", "TXS_PROTO_SHIFT"]
+           "TXS_L4_SHORT", "TXS_PROTO_SHIFT",
+           "tx_frame_count", "tx_frame_plan_dev", "tx_frame_dev", "tx_frame_host", "txf_last_launch", "TXF_EXPORTS",
+           "TXF_L2_DTYPE", "TXF_F_FCS", "TXF_F_HONOR_DF", "TXF_F_L2_ONE", "TXF_WHOLE", "TXF_FRAGMENTED", "TXF_BAD_HDR",
+           "TXF_BAD_LEN", "TXF_REFRAG", "TXF_DF_DROP", "TXF_NO_ROOM"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -66,6 +69,15 @@ TXS_IP_CSUM_SET, TXS_FRAG, TXS_L4_CSUM_SET, TXS_L4_SHORT = 0x020, 0x040, 0x080, 
 TXS_PROTO_SHIFT = 16
 # struct txs_fields as a numpy structured dtype (8 bytes per frame)
 TXS_FIELDS_DTYPE = [("ip_csum", "<u2"), ("l4_csum", "<u2"), ("fcs", "<u4")]
+
+# include/nstack_txf.h — one-pass TX framing (its own list, as RXV_EXPORTS)
+TXF_EXPORTS = ["ether_tx_frame_count", "ether_tx_frame_plan_dev", "ether_tx_frame_dev", "ether_tx_frame_host",
+               "fcs_debug_txf_last_launch"]
+TXF_F_FCS, TXF_F_HONOR_DF, TXF_F_L2_ONE = 1, 2, 4
+TXF_WHOLE, TXF_FRAGMENTED, TXF_BAD_HDR, TXF_BAD_LEN = 0x001, 0x002, 0x004, 0x008
+TXF_REFRAG, TXF_DF_DROP, TXF_NO_ROOM = 0x010, 0x020, 0x040
+# struct txf_l2 as a numpy structured dtype (12 bytes per datagram)
+TXF_L2_DTYPE = [("dst", "u1", (6,)), ("src", "u1", (6,))]
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -209,6 +221,11 @@ def _bind(path: str) -> ctypes.CDLL:
         "ether_tx_seal_set_dma_threshold": (u64, [u64]),
         "fcs_debug_txs_route": (i32, [u64, u64, u32, u64, u32, c.c_char_p, u64]),
         "fcs_debug_txs_last_launch": (i32, [c.c_char_p, u64]),
+        "ether_tx_frame_count": (u32, [u32, u32, u32]),
+        "ether_tx_frame_plan_dev": (i32, [vp, u64, vp, vp, u64, u32, u32, vp, vp, vp]),
+        "ether_tx_frame_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
+        "ether_tx_frame_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
+        "fcs_debug_txf_last_launch": (i32, [c.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -738,4 +755,47 @@ def txs_last_launch() -> str:
     """The kernel the last ether_tx_seal launch of this process launched."""
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_txs_last_launch(buf, 32), "fcs_debug_txs_last_launch")
+    return buf.value.decode()
+
+
+# ---- one-pass TX framing (include/nstack_txf.h) ----
+def tx_frame_count(dgram_len: int, hlen: int, mtu: int) -> int:
+    """Frames a datagram of dgram_len bytes with an hlen-byte header becomes at this mtu (host
+    arithmetic; 0 for what rule 1 or the mtu bound refuses)."""
+    return int(load().ether_tx_frame_count(_u32(dgram_len, "dgram_len"), _u32(hlen, "hlen"), _u32(mtu, "mtu")))
+
+
+def tx_frame_plan_dev(dgram, dgram_bytes: int, off, length, n: int, mtu: int, first, flags: int = 0, status=None,
+                      stream=None) -> None:
+    """first[0..n] (u64) = the exclusive prefix sums of the frame counts (first[n] the total), status[i]
+    (u32, optional) = the TXF_* word of rules 1-5. Device arrays; asynchronous on `stream`."""
+    _check(load().ether_tx_frame_plan_dev(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), n, _u32(mtu, "mtu"),
+                                          _u32(flags, "flags"), _ptr(status), _ptr(first), _stream(stream)),
+           "ether_tx_frame_plan_dev")
+
+
+def tx_frame_dev(dgram, dgram_bytes: int, off, length, l2, n: int, mtu: int, first, out, slot: int, slots: int,
+                 flags: int = TXF_F_FCS, flen=None, status=None, fcs=None, stream=None) -> None:
+    """Builds the frames of n datagrams into out + k * slot, datagram i from slot first[i] on. flen and
+    fcs (u32 per slot) and status (u32 per datagram) are optional. Device arrays; asynchronous on `stream`."""
+    _check(load().ether_tx_frame_dev(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), n, _u32(mtu, "mtu"),
+                                     _u32(flags, "flags"), _ptr(first), _ptr(out), slot, slots, _ptr(flen),
+                                     _ptr(status), _ptr(fcs), _stream(stream)),
+           "ether_tx_frame_dev")
+
+
+def tx_frame_host(dgram, dgram_bytes: int, off, length, l2, n: int, mtu: int, out, slot: int, slots: int,
+                  flags: int = TXF_F_FCS, flen=None, status=None) -> int:
+    """Host form: plans, builds the frames of a host batch into the host arena `out`, packed from slot 0
+    on, fills flen[k] and status[i] (optional) and returns the number of frames."""
+    return _check(load().ether_tx_frame_host(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), n,
+                                             _u32(mtu, "mtu"), _u32(flags, "flags"), _ptr(out), slot, slots,
+                                             _ptr(flen), _ptr(status)),
+                  "ether_tx_frame_host")
+
+
+def txf_last_launch() -> str:
+    """The kernel the last frame-building launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_txf_last_launch(buf, 32), "fcs_debug_txf_last_launch")
     return buf.value.decode()

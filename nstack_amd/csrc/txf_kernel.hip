@@ -1,0 +1,509 @@
+// txf_kernel.hip — one-pass TX framing for gfx950: IPv4 datagrams in, wire-ready Ethernet frames
+// out, every payload byte read once and written once (include/nstack_txf.h has the rules and the
+// reference lines they restate). The frame walk is rxv_kernel's (rxv_parts.hpp, fcs_crc.hpp): a
+// QUARTER-WAVE per datagram with an outer loop over its fragments; within a frame lane j owns the
+// 96-byte chunk that ends 96 j bytes before the frame END, longer frames are walked in 1536-byte
+// segments counted from the frame end. A full fragment at mtu 1500 (1506 bytes) is one pass.
+//
+// What is new here:
+//   * The frame does not exist yet. Frame position q >= 14 + hlen is datagram byte
+//     q - 14 + j * max (the header length cancels), so a lane loads its chunk from the datagram at
+//     the SOURCE's alignment and aligns it to the frame-end grid (v_alignbyte), as the other kernels
+//     do. The 14 + hlen bytes in front come from a header image held in registers: lane l of the
+//     row holds dwords l and l + 16 of the frame's first 128 bytes, built once per datagram from
+//     its first dwords and the MAC record, with ip_len, ip_foff and the checksum zeroed. Their sum
+//     is reduced once per datagram; per fragment the three fields are ORed in:
+//       csum = ~fold(header sum + ip_len + ip_foff)            (one's-complement, memory grid)
+//     The one or two lanes whose chunk holds header bytes fetch those dwords by ds_bpermute and
+//     merge them by byte mask. Padding (I < 56) and the bytes in front of the frame are masked to
+//     zero; the CRC chains then run over the words exactly as they will be stored.
+//   * Two byte alignments meet. The destination of a chunk is out + k * slot + position, whose
+//     low two bits change from slot to slot when slot is no multiple of 4. The chunk's words are
+//     aligned a second time, to the DESTINATION's dword grid: dword t of a lane holds chunk bytes
+//     [4 t - rd, 4 t - rd + 4), the bytes in front of a chunk come from the neighbouring lane's last
+//     word (one ds_bpermute) or, for lane 15, from the previous segment's lane 0 (carried). Stores
+//     are 16-byte stores of four dwords on that grid.
+//   * Edges. The neighbouring slot belongs to another quarter-wave, so the frame's first and last
+//     partial dword are written by byte stores: the up to three bytes in front of the first whole
+//     dword are MAC bytes every lane knows; the up to three bytes behind the last whole dword go
+//     out together with the four FCS bytes, one byte per lane.
+//   * Work. Datagrams differ by three orders of magnitude (one frame or 8185), so rows are not
+//     given datagrams i mod the grid: a row takes a run of kRun consecutive datagrams from a
+//     zeroed device counter (one atomicAdd per wave for all its rows that ran dry, no waiting on
+//     anybody) and comes back for the next run when it is done.
+// Reads stay inside [lo4, hi4) of the datagram arena: a chunk window that crosses its edge is
+// loaded dword by dword under a guard (the batch's first and last datagram at most).
+//
+// The plan kernels (status and exclusive prefix sums of the frame counts) follow below: counts and
+// block totals, a one-workgroup scan of the totals, the add; no workgroup waits for another.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "fcs_crc.hpp"
+#include "fcs_tables.hpp"
+#include "rxv_parts.hpp"
+#include "txf_launch.hpp"
+
+namespace txf {
+
+using fcs::kChunkBytes;
+using fcs::kChunkWords;
+using fcs::kGroup;
+using fcs::kSegBytes;
+using fcs::u32x4a4;
+using rxv::fold64;
+using rxv::keep_range;
+using rxv::row_get;
+using rxv::row_sum;
+using rxv::swap16;
+
+template <typename T>
+__device__ __forceinline__ void gstore(uint64_t addr, T v) {
+    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
+}
+
+// Two independent 12-word chains over a chunk, merged with A_48 (as txs_kernel.hip's).
+__device__ __forceinline__ uint32_t chunk_crc(const uint8_t *lds, const uint32_t (&w)[kChunkWords], uint32_t x0,
+                                              uint32_t tb0, uint32_t tb1) {
+    uint32_t xa = x0 ^ w[0], xb = w[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        xa = fcs::step4(lds, xa, i < 11 ? w[i + 1] : 0u, tb0, tb1);
+        xb = fcs::step4(lds, xb, i < 11 ? w[13 + i] : 0u, tb0, tb1);
+    }
+    return fcs::uniform_shift<fcs::kLdsH48>(lds, xa, xb);
+}
+
+// A datagram that becomes frames (uniform over the row but for the image).
+struct Dg {
+    uint64_t src;      // the address frame position 0 of fragment 0 maps to: datagram address - 14
+    uint64_t slot0;    // its first slot
+    uint32_t D, hlen, cnt;
+    uint32_t max;      // 0: TXF_WHOLE
+    uint32_t img0, img1;   // lane l: dwords l and l + 16 of the frame's first 128 bytes; ip_len, ip_foff, checksum zero
+    uint32_t hsum;     // folded sum of the image's header bytes [14, 14 + hlen)
+    uint32_t keep;     // the datagram's own ip_len | ip_foff << 16, as they lie in memory (TXF_WHOLE)
+};
+
+struct Frame {
+    uint64_t fo;       // address of the frame's first byte
+    uint64_t src;      // the address frame position 0 maps to in the datagram arena
+    uint32_t F, I, m;  // frame bytes, IP bytes, segments
+    uint32_t f0;       // img0 with this frame's ip_len, ip_foff and checksum
+};
+
+struct Pos {
+    uint32_t jf, k;    // fragment, segment
+    bool act;
+    Dg g;
+    Frame fr;
+};
+
+constexpr uint64_t kRun = 8;   // datagrams a row takes from the work counter at a time
+
+struct Chunk {
+    u32x4a4 x[6];
+    uint32_t x6;
+    uint32_t r;        // source address of the chunk's first byte & 3
+};
+
+__device__ __forceinline__ int rel_of(const Pos &c, int j) {   // frame position of the chunk's first byte
+    return (int)c.fr.F - kSegBytes * (int)(c.fr.m - 1u - c.k) - kChunkBytes * (j + 1);
+}
+
+template <bool FCSW, int NT>
+__global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[FCSW ? fcs::kLdsBytes : 16];
+    if (FCSW) {
+        fcs::KParams kp{};
+        kp.blob = p.blob;
+        fcs::stage_tables<NT>(kp, lds);
+    }
+    const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
+    uint32_t tb0, tb1;
+    fcs::table_bases(lane, tb0, tb1);
+    const uint32_t lanebase = fcs::kLdsLane | ((uint32_t)(lane & 31) * 4u);
+    // this row's run of datagrams [cur, end), taken from p.ctr
+    uint64_t cur = 0, end = 0;
+    auto take = [&](bool want) {   // wave-uniform call: every row with `want` gets the next run
+        const uint64_t m = __ballot(want && j == 0);
+        if (m == 0) return;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        unsigned long long base = 0;
+        if (lane == leader) base = atomicAdd(p.ctr, (unsigned long long)__popcll(m) * kRun);
+        base = __shfl(base, leader, 64);
+        const uint64_t before = m & ((1ull << (lane & ~(kGroup - 1))) - 1ull);   // wanting rows in front of this one
+        if (want) {
+            cur = base + (uint64_t)__popcll(before) * kRun;
+            end = cur + kRun < p.n ? cur + kRun : p.n;
+        }
+    };
+
+    auto frame_of = [&](const Dg &g, uint32_t jf) -> Frame {
+        Frame f;
+        const bool whole = g.max == 0u;
+        const uint32_t B = g.D - g.hlen, at = jf * g.max;
+        const uint32_t plen = B - at < g.max ? B - at : g.max;
+        f.I = whole ? g.D : g.hlen + plen;
+        const uint32_t fo16 = (jf + 1u < g.cnt ? 0x2000u : 0u) | (at >> 3);
+        const uint32_t lenw = whole ? (g.keep & 0xffffu) : swap16(f.I);
+        const uint32_t foffw = whole ? (g.keep >> 16) : swap16(fo16);
+        const uint32_t csum = ~fold64((uint64_t)g.hsum + lenw + foffw) & 0xffffu;   // rule 7
+        f.f0 = g.img0 | (j == 4 ? lenw : 0u) | (j == 5 ? foffw : 0u) | (j == 6 ? csum : 0u);
+        f.F = frame_len(f.I);
+        f.m = (f.F + (uint32_t)kSegBytes - 1u) / (uint32_t)kSegBytes;
+        f.fo = p.out + (g.slot0 + jf) * p.slot;
+        f.src = g.src + at;
+        return f;
+    };
+
+    // Datagram i: rules 1-6 and 9, its status word, and (where it becomes frames) its header image.
+    auto load_dg = [&](uint64_t i) -> Dg {
+        Dg g{};
+        const uint64_t a = p.dg + p.off[i];
+        const uint32_t D = p.len[i], r = (uint32_t)a & 3u;
+        const uint64_t a4 = a & ~3ull, he = (a + D + 3ull) & ~3ull;
+        const uint64_t ha = a4 + 4ull * (uint32_t)j;
+        uint32_t h0 = 0u, h1 = 0u;   // dwords j and j + 16 from floor4(datagram), inside it and the arena
+        if (ha >= p.lo4 && ha + 4 <= he && ha + 4 <= p.hi4) h0 = fcs::gload<uint32_t>(ha);
+        if (ha + 64 >= p.lo4 && ha + 68 <= he && ha + 68 <= p.hi4) h1 = fcs::gload<uint32_t>(ha + 64);
+        const uint32_t e0 = row_get(h0, 0u), e1 = row_get(h0, 1u), e2 = row_get(h0, 2u);
+        const uint32_t w0 = __builtin_amdgcn_alignbyte(e1, e0, r);   // vhl, tos, ip_len
+        const uint32_t w4 = __builtin_amdgcn_alignbyte(e2, e1, r);   // id, ip_foff
+        One o = plan_fields(D, w0 & 0xffu, swap16(w0 >> 16), swap16(w4 >> 16), p.mtu, p.flags);
+        g.slot0 = p.first[i];
+        if (o.cnt && (g.slot0 > p.slots || o.cnt > p.slots - g.slot0)) {   // rule 9
+            o.status |= kNoRoom;
+            o.cnt = 0u;
+        }
+        if (j == 0 && p.status != nullptr) p.status[i] = o.status;
+        g.cnt = o.cnt;
+        if (!o.cnt) return g;
+        g.D = D;
+        g.hlen = o.hlen;
+        g.max = o.max;
+        g.src = a - 14ull;
+        g.keep = (w0 >> 16) | (w4 & 0xffff0000u);
+        // frame dword d holds frame bytes 4 d .. 4 d + 3 = datagram bytes 4 d - 14 ..: dwords
+        // d - 4 + c and the next of the datagram's grid, shifted by (2 + r) & 3
+        const uint32_t c = (2u + r) >> 2, sh = (2u + r) & 3u;
+        auto hget = [&](int e) -> uint32_t {
+            const uint32_t v0 = row_get(h0, (uint32_t)e & 15u), v1 = row_get(h1, (uint32_t)e & 15u);
+            return e < 0 ? 0u : (e < 16 ? v0 : v1);
+        };
+        const int e = j - 4 + (int)c;
+        g.img0 = __builtin_amdgcn_alignbyte(hget(e + 1), hget(e), sh);
+        g.img1 = __builtin_amdgcn_alignbyte(hget(e + 17), hget(e + 16), sh);
+        if (j < 3) {   // the MAC pair, rule 8
+            const uint8_t *m = p.l2 + 12ull * ((p.flags & kFlagL2One) ? 0ull : i) + 4u * (uint32_t)j;
+            g.img0 = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
+        }
+        if (j == 3) g.img0 = (g.img0 & 0xffff0000u) | 0x0008u;          // 08 00
+        if (j >= 4 && j <= 6) g.img0 &= 0xffff0000u;                     // ip_len, ip_foff, checksum
+        const int hend = 14 + (int)o.hlen;
+        const uint32_t k0 = keep_range(g.img0, 4 * j, 14, hend), k1 = keep_range(g.img1, 64 + 4 * j, 14, hend);
+        g.hsum = fold64(row_sum((k0 & 0xffffu) + (k0 >> 16) + (k1 & 0xffffu) + (k1 >> 16)));
+        return g;
+    };
+
+    // The row's next datagram that becomes frames; rows with `go` only.
+    auto advance = [&](Pos &n, bool go) {
+        while (__any(go)) {
+            take(go && cur >= end);
+            if (go) {
+                if (cur >= p.n) {
+                    n.act = false;
+                    n.k = 0;
+                    n.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
+                    go = false;
+                } else {
+                    const Dg g = load_dg(cur++);
+                    if (g.cnt) {
+                        n.g = g;
+                        n.jf = 0;
+                        n.k = 0;
+                        n.act = true;
+                        n.fr = frame_of(g, 0u);
+                        go = false;
+                    }
+                }
+            }
+        }
+    };
+
+    auto next = [&](const Pos &c) -> Pos {
+        Pos n = c;
+        bool adv = false;
+        if (c.act) {
+            n.k = c.k + 1u;
+            if (n.k >= c.fr.m) {
+                n.k = 0;
+                n.jf = c.jf + 1u;
+                if (n.jf >= c.g.cnt) adv = true;
+                else n.fr = frame_of(n.g, n.jf);
+            }
+        }
+        if (__any(adv)) advance(n, adv);
+        return n;
+    };
+
+    auto issue = [&](const Pos &c, Chunk &ch) {
+        const int rel = rel_of(c, j);
+        const uint64_t sa = c.fr.src + (uint64_t)(int64_t)rel, a4 = sa & ~3ull;
+        ch.r = (uint32_t)sa & 3u;
+#pragma unroll
+        for (int q = 0; q < 6; q++) ch.x[q] = u32x4a4{0u, 0u, 0u, 0u};
+        ch.x6 = 0u;
+        if (c.act && rel > -kChunkBytes) {
+            if (a4 >= p.lo4 && a4 + 4 * (kChunkWords + 1) <= p.hi4) {
+                fcs::LoadPriority lp;
+#pragma unroll
+                for (int q = 0; q < 6; q++) ch.x[q] = fcs::gload<u32x4a4>(a4 + 16 * q);
+                ch.x6 = fcs::gload<uint32_t>(a4 + 96);
+            } else {   // a window across the arena's edge: dword by dword
+                uint32_t d[kChunkWords + 1];
+#pragma unroll
+                for (int q = 0; q <= kChunkWords; q++) {
+                    const uint64_t ad = a4 + 4 * q;
+                    d[q] = (ad >= p.lo4 && ad + 4 <= p.hi4) ? fcs::gload<uint32_t>(ad) : 0u;
+                }
+#pragma unroll
+                for (int q = 0; q < 6; q++) ch.x[q] = u32x4a4{d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
+                ch.x6 = d[kChunkWords];
+            }
+        }
+    };
+
+    // per-frame state, carried over the frame's segments
+    uint32_t s = 0;       // CRC register
+    uint32_t carry = 0;   // the last word of the previous segment's lane 0 (the bytes in front of lane 15's chunk)
+
+    auto process = [&](const Pos &c, const Chunk &ch) {
+        const Frame &fr = c.fr;
+        const int rel = rel_of(c, j);
+        const bool first = c.k == 0, last = c.act && c.k + 1u == fr.m;
+        uint32_t d[kChunkWords + 1];
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            d[4 * q] = ch.x[q].x;
+            d[4 * q + 1] = ch.x[q].y;
+            d[4 * q + 2] = ch.x[q].z;
+            d[4 * q + 3] = ch.x[q].w;
+        }
+        d[kChunkWords] = ch.x6;
+        uint32_t w[kChunkWords];   // word i: frame positions rel + 4 i ..
+#pragma unroll
+        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], ch.r);
+        // ---- the 14 + hlen bytes in front: from the header image (a first segment shorter than
+        //      that leaves the rest of them to the second) ----
+        const int hend = 14 + (int)c.g.hlen;
+        if (__any(c.act && rel < hend && rel > -kChunkBytes)) {
+#pragma unroll
+            for (int i = 0; i < kChunkWords; i++) {
+                const int q = rel + 4 * i;
+                const bool hit = c.act && q > -4 && q < hend;
+                if (__any(hit)) {
+                    const int D0 = q >> 2, D1 = D0 + 1;   // -1 where the word starts in front of the frame: masked below
+                    uint32_t lo = row_get(fr.f0, (uint32_t)D0 & 15u), hi = row_get(fr.f0, (uint32_t)D1 & 15u);
+                    if (__any(hit && D1 >= 16)) {
+                        const uint32_t lo1 = row_get(c.g.img1, (uint32_t)D0 & 15u), hi1 = row_get(c.g.img1, (uint32_t)D1 & 15u);
+                        lo = D0 >= 16 ? lo1 : lo;
+                        hi = D1 >= 16 ? hi1 : hi;
+                    }
+                    const uint32_t hv = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)q & 3u);
+                    const uint32_t pm = fcs::clear_low_bits(0xFFFFFFFFu, 8 * (hend - q));   // bytes from hend on: payload
+                    if (hit) w[i] = (w[i] & pm) | (hv & ~pm);
+                }
+            }
+        }
+        // ---- padding (rule 8): positions from 14 + I on are zero ----
+        if (__any(c.act && fr.I < 56u)) {
+            const int pe = 14 + (int)fr.I;
+#pragma unroll
+            for (int i = 0; i < kChunkWords; i++) w[i] ^= fcs::clear_low_bits(w[i], 8 * (pe - (rel + 4 * i)));
+        }
+        // ---- the front mask: positions in front of the frame ----
+        if (first) {
+#pragma unroll
+            for (int i = 0; i < kChunkWords; i++) w[i] = fcs::clear_low_bits(w[i], -8 * (rel + 4 * i));
+        }
+        // ---- CRC over the words as they will be stored ----
+        uint32_t crc = 0u;
+        if (FCSW) {
+            uint32_t x0 = 0u;
+            if (first) {
+                const int zr = -rel, zi = zr < 0 ? 0 : (zr > kChunkBytes - 1 ? kChunkBytes - 1 : zr);
+                const uint32_t iv = fcs::lds_rd(lds, fcs::kLdsInv + 4u * (uint32_t)zi);
+                x0 = (zr >= 0 && zr < kChunkBytes) ? iv : 0u;
+            }
+            const uint32_t rr = chunk_crc(lds, w, x0, tb0, tb1);
+            s = first ? rr : fcs::uniform_shift<fcs::kLdsJump>(lds, s, rr);
+            if (__any(last)) crc = ~fcs::row_xor(last ? fcs::lane_shift(lds, s, lanebase) : 0u);
+        }
+        // ---- stores, on the destination's dword grid ----
+        const uint64_t da = fr.fo + (uint64_t)(int64_t)rel;
+        const uint32_t rd = (uint32_t)da & 3u;
+        const uint64_t A0 = da - rd;
+        const uint32_t up = row_get(w[kChunkWords - 1], (uint32_t)(j + 1) & 15u);
+        const uint32_t prevw = j == kGroup - 1 ? carry : up;
+        carry = row_get(w[kChunkWords - 1], 0u);
+        uint32_t dst[kChunkWords];   // dword t: chunk bytes [4 t - rd, 4 t - rd + 4)
+#pragma unroll
+        for (int t = 0; t < kChunkWords; t++) {
+            const uint32_t al = __builtin_amdgcn_alignbyte(w[t], t ? w[t - 1] : prevw, 4u - rd);
+            dst[t] = rd ? al : w[t];
+        }
+        if (c.act) {
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const uint64_t ad = A0 + 16 * q;
+                if (ad >= fr.fo) {
+                    gstore<u32x4a4>(ad, u32x4a4{dst[4 * q], dst[4 * q + 1], dst[4 * q + 2], dst[4 * q + 3]});
+                } else if (ad + 16 > fr.fo) {   // the frame's first dwords
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (ad + 4 * e >= fr.fo) gstore<uint32_t>(ad + 4 * e, dst[4 * q + e]);
+                }
+            }
+        }
+        // the frame's first partial dword: MAC bytes, by byte stores
+        if (__any(c.act && first)) {
+            const uint32_t mac0 = row_get(fr.f0, 0u);
+            const uint32_t nb = (4u - ((uint32_t)fr.fo & 3u)) & 3u;
+            if (c.act && first && (uint32_t)j < nb) gstore<uint8_t>(fr.fo + (uint32_t)j, (uint8_t)(mac0 >> (8 * j)));
+        }
+        // the frame's last partial dword and the FCS, by byte stores; flen and fcs of its slot
+        if (__any(last)) {
+            uint64_t tv = rd ? (uint64_t)(carry >> (8u * (4u - rd))) : 0ull;
+            tv |= (uint64_t)crc << (8u * rd);
+            const uint32_t nbt = rd + (FCSW ? 4u : 0u);
+            if (last && (uint32_t)j < nbt) gstore<uint8_t>(fr.fo + fr.F - rd + (uint32_t)j, (uint8_t)(tv >> (8 * j)));
+            const uint64_t slotk = c.g.slot0 + c.jf;
+            if (last && j == 15 && p.flen != nullptr) p.flen[slotk] = fr.F;
+            if (last && j == 14 && p.fcs != nullptr) p.fcs[slotk] = crc;
+        }
+    };
+
+    Pos A, B;
+    A.jf = A.k = 0;
+    A.act = false;
+    A.g = Dg{};
+    A.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
+    advance(A, true);
+    Chunk CA, CB;
+    issue(A, CA);
+    // two items in flight per lane: process one while the other's loads are outstanding
+    while (__any(A.act)) {
+        B = next(A);
+        issue(B, CB);
+        process(A, CA);
+        if (!__any(B.act)) break;
+        A = next(B);
+        issue(A, CA);
+        process(B, CB);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan: status words and the exclusive prefix sums of the frame counts.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int o = 1; o < kPlanThreads; o <<= 1) {
+        const uint64_t add = t >= o ? sh[t - o] : 0ull;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    return sh[t];
+}
+
+// first[i] = the frame count of datagram i; tot[block] = the block's sum.
+__global__ __launch_bounds__(kPlanThreads) void txf_plan_kernel(FParams p, uint32_t *status, uint64_t *first,
+                                                                uint64_t *tot) {
+    __shared__ uint64_t sh[kPlanThreads];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    uint64_t cnt = 0;
+    if (i < p.n) {
+        const uint64_t a = p.dg + p.off[i], a4 = a & ~3ull;
+        const uint32_t D = p.len[i], r = (uint32_t)a & 3u;
+        uint32_t e[3] = {0u, 0u, 0u};
+        if (D >= 20u) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const uint64_t ad = a4 + 4 * q;
+                if (ad >= p.lo4 && ad + 4 <= p.hi4) e[q] = fcs::gload<uint32_t>(ad);
+            }
+        }
+        const uint32_t w0 = __builtin_amdgcn_alignbyte(e[1], e[0], r), w4 = __builtin_amdgcn_alignbyte(e[2], e[1], r);
+        const One o = plan_fields(D, w0 & 0xffu, swap16(w0 >> 16), swap16(w4 >> 16), p.mtu, p.flags);
+        if (status != nullptr) status[i] = o.status;
+        first[i] = o.cnt;
+        cnt = o.cnt;
+    }
+    const uint64_t incl = block_scan_incl(cnt, sh);
+    if (threadIdx.x == kPlanThreads - 1) tot[blockIdx.x] = incl;
+}
+
+// One workgroup: tot[b] becomes the sum of the blocks in front of b; *total the sum of all.
+__global__ __launch_bounds__(kPlanThreads) void txf_scan_totals_kernel(uint64_t *tot, uint64_t nb, uint64_t *total) {
+    __shared__ uint64_t sh[kPlanThreads];
+    uint64_t base = 0;
+    for (uint64_t b0 = 0; b0 < nb; b0 += kPlanThreads) {
+        const uint64_t b = b0 + threadIdx.x;
+        const uint64_t v = b < nb ? tot[b] : 0ull;
+        const uint64_t incl = block_scan_incl(v, sh);
+        if (b < nb) tot[b] = base + incl - v;
+        base += sh[kPlanThreads - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = base;
+}
+
+// first[i] = tot[block] + the counts in front of i within the block.
+__global__ __launch_bounds__(kPlanThreads) void txf_add_kernel(uint64_t *first, const uint64_t *tot, uint64_t n) {
+    __shared__ uint64_t sh[kPlanThreads];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    const uint64_t v = i < n ? first[i] : 0ull;
+    const uint64_t incl = block_scan_incl(v, sh);
+    if (i < n) first[i] = tot[blockIdx.x] + incl - v;
+}
+
+namespace {
+std::atomic<int> g_last_route{(int)Route::kNone};
+}
+Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
+
+hipError_t launch_txf(const FParams &p, int cus, hipStream_t st) {
+    (void)hipGetLastError();   // report this launch's own error, not an earlier call's
+    if (!p.n) return hipSuccess;
+    if (!p.ctr) return hipErrorInvalidValue;
+    const bool fcsw = (p.flags & kFlagFcs) != 0;
+    g_last_route.store((int)(fcsw ? Route::kGeneralFcs : Route::kGeneral), std::memory_order_relaxed);
+    // one workgroup per CU, persistent over the datagrams (a quarter-wave per run of datagrams)
+    const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
+    const int grid = (int)(want < (uint64_t)cus ? want : (uint64_t)cus);
+    if (fcsw) hipLaunchKernelGGL((txf_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else hipLaunchKernelGGL((txf_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_plan(const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
+    (void)hipGetLastError();
+    if (!p.n) return hipSuccess;
+    const uint64_t nb = (p.n + kPlanThreads - 1) / kPlanThreads;
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(txf_plan_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p, status, first, tot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(txf_scan_totals_kernel, dim3(1), dim3(kPlanThreads), 0, st, tot, nb, first + p.n);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(txf_add_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, first, (const uint64_t *)tot, p.n);
+    return hipGetLastError();
+}
+
+}  // namespace txf

@@ -1,0 +1,41 @@
+// txf_launch.hpp — host-side launchers of one-pass TX framing (txf_kernel.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "txf_plan.hpp"
+
+namespace txf {
+
+// What both kernels read: datagram i = [dg + off[i], + len[i]); [lo4, hi4) is the readable range of
+// the datagram arena, dword-rounded.
+struct FParams {
+    uint64_t dg;
+    uint64_t lo4, hi4;
+    const uint64_t *off;
+    const uint32_t *len;
+    uint64_t n;
+    uint32_t mtu, flags;
+    // frame building only
+    const uint8_t *l2;       // 12-byte records
+    const uint64_t *first;
+    uint64_t out, slot, slots;
+    uint32_t *flen, *status, *fcs;   // each may be null
+    const uint32_t *blob;    // the FCS engine's constant tables (kFlagFcs only)
+    unsigned long long *ctr; // zeroed device work counter (fcs::launch_with_counter): rows take runs of datagrams from it
+};
+
+constexpr int kThreads = 512;       // txf_kernel: 8 waves per CU, a quarter-wave per datagram
+constexpr int kPlanThreads = 256;   // the plan kernels: one datagram per thread
+
+enum class Route { kNone, kGeneral, kGeneralFcs };
+Route last_launch();   // what the last launch_txf of this process launched (tests)
+
+// Builds the frames of p.n datagrams on a grid of at most `cus` workgroups; needs p.ctr.
+hipError_t launch_txf(const FParams &p, int cus, hipStream_t st);
+
+// status[i] (may be null) and first[0..n]: counts and per-block totals, the scan of the totals in
+// one workgroup, the add; three launches on `st`. tot holds ceil(n / kPlanThreads) u64 of scratch.
+hipError_t launch_plan(const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st);
+
+}  // namespace txf
