@@ -81,6 +81,8 @@ int copy_name(const char *r, char *out, uint64_t cap) {
 constexpr uint64_t kInBytes = 32ull << 20;     // a chunk's datagrams
 constexpr uint64_t kOutBytes = 64ull << 20;    // a chunk's slots
 constexpr uint64_t kChunkDgs = 1ull << 18;
+// Sizes the flen staging only; as a bound on a chunk it cannot bind: at the smallest slot (70 bytes)
+// 2^20 frames are 70 MiB, more than kOutBytes, so the slot bound always cuts first.
 constexpr uint64_t kChunkFrames = 1ull << 20;
 constexpr int kDepth = 2;
 

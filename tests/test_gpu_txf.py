@@ -4,7 +4,6 @@ arenas, equal to the model's (tests/txf_model.py: the header's rules with the or
 checksum) and to the independently generated golden vectors. The output arena is canary bytes
 before, between and behind the slots and is compared as a whole, so a write to any byte other than
 a produced frame's fails the test; flen, fcs, status and first are compared with the model too."""
-import functools
 import struct
 import threading
 
@@ -14,13 +13,11 @@ import pytest
 import nstack_amd as na
 import rxv_model as rm
 import txf_model as fm
+from txf_batch import FCS, UNSET, Batch, datagram, frames_fn, to_dev
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-FCS = fm.F_FCS
-UNSET = 0xCCCCCCCC
 
 
 @pytest.fixture(scope="module")
@@ -35,131 +32,6 @@ def dev():
 @pytest.fixture(scope="module")
 def txf_golden():
     return fm.load_golden()
-
-
-_ORACLES = {}
-
-
-@functools.lru_cache(maxsize=None)
-def _frames(dg, mac, mtu, flags):
-    return fm.frames(_ORACLES["fcs"], _ORACLES["inet"], dg, mac, mtu, flags)
-
-
-def frames_fn(fcs_oracle, inet_oracle, dg, mac, mtu, flags):
-    """fm.frames, memoised: the frames of a datagram do not depend on where they are placed."""
-    _ORACLES["fcs"], _ORACLES["inet"] = fcs_oracle, inet_oracle
-    return _frames(bytes(dg), bytes(mac), mtu, flags)
-
-
-def to_dev(arr, dev):
-    return torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
-
-
-def datagram(rng, hlen, B, foff=0, vhl=None, ip_len=None, proto=253):
-    """An IPv4 datagram of random bytes: options, payload and the checksum field are garbage."""
-    D = hlen + B
-    b = bytearray(rng.integers(0, 256, D, dtype=np.uint8).tobytes())
-    b[0] = (0x40 | hlen // 4) if vhl is None else vhl
-    b[2:4] = int(D if ip_len is None else ip_len).to_bytes(2, "big")
-    b[6:8] = int(foff).to_bytes(2, "big")
-    b[9] = proto
-    return bytes(b)
-
-
-def pack(dgs, seed=1, aligns=None):
-    """Datagrams into one arena of random bytes, datagram i at aligns[i] mod 4 (random by default)."""
-    rng = np.random.default_rng(seed)
-    arena = rng.integers(0, 256, sum(len(d) + 8 for d in dgs) + 16, dtype=np.uint8)
-    off, pos = [], 0
-    for i, d in enumerate(dgs):
-        a = int(rng.integers(0, 4)) if aligns is None else aligns[i]
-        pos += (a - pos) % 4
-        off.append(pos)
-        arena[pos:pos + len(d)] = np.frombuffer(d, dtype=np.uint8)
-        pos += len(d) + int(rng.integers(0, 4))
-    return arena[:pos].copy(), np.array(off, dtype=np.uint64), np.array([len(d) for d in dgs], dtype=np.uint32)
-
-
-def macs_of(n, seed=2):
-    return np.random.default_rng(seed).integers(0, 256, (n, 12), dtype=np.uint8)
-
-
-class Batch:
-    """A batch and the model's result for one placement."""
-
-    def __init__(self, oracle, inet_oracle, dgs, mtu, flags=FCS, slot=None, slots=None, first=None, base=0, seed=1,
-                 aligns=None, l2=None, spare=0):
-        self.mtu, self.flags = mtu, flags
-        self.arena, self.off, self.ln = pack(dgs, seed, aligns)
-        self.n = len(dgs)
-        self.l2 = macs_of(self.n, seed + 1) if l2 is None else l2
-        self.slot = fm.min_slot(mtu, flags) if slot is None else slot
-        total = sum(fm.plan(d, mtu, flags)[1] for d in dgs)
-        self.slots = total + spare if slots is None else slots
-        self.first = first
-        self.base = 64 + base                      # canary bytes in front of slot 0; `base` sets out's alignment
-        rng = np.random.default_rng(seed + 7)
-        self.out0 = rng.integers(0, 256, self.base + self.slots * self.slot + 64, dtype=np.uint8)
-        exp = self.out0.copy()
-        body, self.flen, self.fcs, self.status, self.plan_first = fm.build(
-            oracle, inet_oracle, self.arena, self.off, self.ln, self.l2, mtu, flags, self.out0[self.base:], self.slot,
-            self.slots, first, frames_fn)
-        exp[self.base:] = body
-        self.expect = exp
-        self.total = total
-
-    def run_dev(self, dev, plan=True, flen=True, status=True, fcs=True, stream=None):
-        """(arena after, flen, fcs, status, planned first, planned status) of plan_dev + frame_dev."""
-        if stream is not None:   # the tensors are made and filled on the stream the library works on
-            with torch.cuda.stream(stream):
-                return self._run_dev(dev, plan, flen, status, fcs, stream)
-        return self._run_dev(dev, plan, flen, status, fcs, None)
-
-    def _run_dev(self, dev, plan, flen, status, fcs, stream):
-        d_arena, d_off, d_ln, d_l2 = (to_dev(x, dev) for x in (self.arena, self.off, self.ln, self.l2))
-        d_out = to_dev(self.out0, dev)
-        d_first = torch.full((self.n + 1,), 0x5555555555555555, dtype=torch.int64, device=dev)
-        d_pst = torch.full((max(self.n, 1),), -1, dtype=torch.int32, device=dev)
-        if plan:
-            na.tx_frame_plan_dev(d_arena, self.arena.size, d_off, d_ln, self.n, self.mtu, d_first, self.flags, d_pst,
-                                 stream=stream)
-        use_first = d_first if self.first is None else to_dev(np.asarray(self.first, dtype=np.uint64), dev)
-        d_flen = torch.full((max(self.slots, 1),), UNSET - (1 << 32), dtype=torch.int32, device=dev)
-        d_fcs = torch.full((max(self.slots, 1),), UNSET - (1 << 32), dtype=torch.int32, device=dev)
-        d_st = torch.full((max(self.n, 1),), -1, dtype=torch.int32, device=dev)
-        na.tx_frame_dev(d_arena, self.arena.size, d_off, d_ln, d_l2, self.n, self.mtu, use_first,
-                        d_out.data_ptr() + self.base, self.slot, self.slots, self.flags, d_flen if flen else None,
-                        d_st if status else None, d_fcs if fcs else None, stream=stream)
-        if stream is not None:
-            stream.synchronize()
-        else:
-            torch.cuda.synchronize()
-        u32 = lambda t, k: t.cpu().numpy().view(np.uint32)[:k]
-        return (d_out.cpu().numpy(), u32(d_flen, self.slots), u32(d_fcs, self.slots), u32(d_st, self.n),
-                d_first.cpu().numpy().view(np.uint64), u32(d_pst, self.n))
-
-    def run_host(self):
-        out = self.out0.copy()
-        flen = np.full(max(self.slots, 1), UNSET, dtype=np.uint32)
-        st = np.full(max(self.n, 1), 0xFFFFFFFF, dtype=np.uint32)
-        k = na.tx_frame_host(self.arena, self.arena.size, self.off, self.ln, self.l2, self.n, self.mtu,
-                             out[self.base:], self.slot, self.slots, self.flags, flen, st)
-        return out, flen[:self.slots], st[:self.n], k
-
-    def check(self, dev, host=True):
-        out, flen, fcs, st, first, pst = self.run_dev(dev)
-        diff = np.flatnonzero(out != self.expect)
-        assert diff.size == 0, ("device form", diff[:8], [(int(d) - self.base) // self.slot for d in diff[:8]])
-        assert (flen == self.flen).all() and (fcs == self.fcs).all()
-        assert (st == self.status).all(), (st[:8], self.status[:8])
-        assert (first == self.plan_first).all()
-        assert (pst == self.status & ~np.uint32(fm.NO_ROOM)).all()
-        if host and self.first is None and self.total <= self.slots:
-            hout, hflen, hst, k = self.run_host()
-            assert k == self.total
-            diff = np.flatnonzero(hout != self.expect)
-            assert diff.size == 0, ("host form", diff[:8])
-            assert (hflen == self.flen).all() and (hst == self.status).all()
 
 
 # ---- the golden vectors, at datagram start alignments 0..3 and out base alignments 0..3 ----
@@ -192,35 +64,63 @@ def sweep_lengths(mtu, hlen):
     return list(range(0, top + 1)) if top < 400 else list(range(0, top + 1, 41)) + [mx - 1, mx, mx + 1, 2 * mx, top]
 
 
-@pytest.mark.parametrize("extra", [0, 1, 2, 3])
-@pytest.mark.parametrize("mtu", [100, 1500])
-def test_alignment_sweep(dev, oracle, inet_oracle, mtu, extra):
+def alignment_sweep(dev, oracle, inet_oracle, mtu, extra, flags):
     rng = np.random.default_rng(100 + mtu)
     dgs, res = [], set()
+    T = 4 if flags & FCS else 0
     for hlen in (20, 24, 60):
         for B in sweep_lengths(mtu, hlen):
             dgs.append(datagram(rng, hlen, B))
-            for F in (len(f) - 4 for f in frames_fn(oracle, inet_oracle, dgs[-1], bytes(12), mtu, FCS)[1]):
+            for F in (len(f) - T for f in frames_fn(oracle, inet_oracle, dgs[-1], bytes(12), mtu, flags)[1]):
                 res.add(F % 96)
     # every residue mod 96 of F (at mtu 100 every F there is: 70..114)
     assert res == (set(range(96)) if mtu == 1500 else {F % 96 for F in range(70, 115)})
-    b = Batch(oracle, inet_oracle, dgs, mtu, FCS, slot=fm.min_slot(mtu, FCS) + extra, seed=3)
+    dgs += [datagram(rng, hlen, mtu - hlen) for hlen in (20, 24, 60)]      # whole frames of 14 + mtu, in a row
+    b = Batch(oracle, inet_oracle, dgs, mtu, flags, slot=fm.min_slot(mtu, flags) + extra, seed=3)
     if extra:   # every source-to-destination distance mod 4 occurs within the batch
         dist = set()
         for i in range(b.n):
             dist.add((int(b.off[i]) - (b.base + int(b.plan_first[i]) * b.slot)) & 3)
         assert dist == {0, 1, 2, 3}
+    if not T and not extra:   # full frames in consecutive slots: a frame's last byte abuts the next one's first
+        full = b.flen[:b.total] == b.slot
+        assert (full[:-1] & full[1:]).sum() >= 2
     b.check(dev, host=extra in (0, 3))
 
 
+@pytest.mark.parametrize("extra", [0, 1, 2, 3])
+@pytest.mark.parametrize("mtu", [100, 1500])
+def test_alignment_sweep(dev, oracle, inet_oracle, mtu, extra):
+    alignment_sweep(dev, oracle, inet_oracle, mtu, extra, FCS)
+
+
+@pytest.mark.parametrize("extra", [0, 1, 2, 3])
+@pytest.mark.parametrize("mtu", [100, 1500])
+def test_alignment_sweep_without_fcs(dev, oracle, inet_oracle, mtu, extra):
+    """txf_kernel<false>: the tail store is the up to three bytes behind the last whole dword alone."""
+    alignment_sweep(dev, oracle, inet_oracle, mtu, extra, 0)
+
+
 # ---- segment borders ----
-@pytest.mark.parametrize("mtu", list(range(1528, 1580, 4)) + [3072, 3100, 9000])
-def test_segment_borders(dev, oracle, inet_oracle, mtu):
+BORDER_MTUS = list(range(1528, 1580, 4)) + [3072, 3100, 9000]
+
+
+def segment_borders(dev, oracle, inet_oracle, mtu, flags):
     rng = np.random.default_rng(mtu)
     dgs = [datagram(rng, hlen, 2 * mtu + 5 - hlen) for hlen in (20, 24, 60)]
     dgs += [datagram(rng, 20, mtu - 20), datagram(rng, 28, mtu - 29)]      # whole frames of 14 + mtu and one less
     for slot_extra in (0, 1):
-        Batch(oracle, inet_oracle, dgs, mtu, FCS, slot=fm.min_slot(mtu, FCS) + slot_extra, seed=mtu).check(dev)
+        Batch(oracle, inet_oracle, dgs, mtu, flags, slot=fm.min_slot(mtu, flags) + slot_extra, seed=mtu).check(dev)
+
+
+@pytest.mark.parametrize("mtu", BORDER_MTUS)
+def test_segment_borders(dev, oracle, inet_oracle, mtu):
+    segment_borders(dev, oracle, inet_oracle, mtu, FCS)
+
+
+@pytest.mark.parametrize("mtu", BORDER_MTUS)
+def test_segment_borders_without_fcs(dev, oracle, inet_oracle, mtu):
+    segment_borders(dev, oracle, inet_oracle, mtu, 0)
 
 
 # ---- extremes ----

@@ -235,6 +235,29 @@ def test_host_form_checks_the_arena_and_the_capacity_before_any_work():
     assert L.ether_tx_frame_host(p(dgram), dgram.size, p(off), p(ln), p(l2), 0, 1500, 1, p(out), 1600, 0, None, None) == 0
 
 
+def test_host_form_refuses_a_datagram_larger_than_a_chunk_before_any_work():
+    """65535 bytes with a 60-byte header at mtu 76 are 8185 frames; in slots of 16 KiB they are more
+    than the 64 MiB of slots one chunk of the host pipeline holds."""
+    L = na.load()
+    D, slot, slots = 65535, 16384, 8185
+    small = struct.pack(">BBHHHBBHII", 0x45, 0, 40, 1, 0, 64, 17, 0, 1, 2) + bytes(20)
+    big = struct.pack(">BBHHHBBHII", 0x4F, 0, D, 1, 0, 64, 17, 0, 1, 2) + bytes(D - 20)
+    assert na.tx_frame_count(D, 60, 76) == slots and slots * slot > 64 << 20 > (slots // 2) * slot
+    dgram = np.frombuffer(small + big, dtype=np.uint8).copy()
+    off = np.array([0, 40], dtype=np.uint64)
+    ln = np.array([40, D], dtype=np.uint32)
+    l2 = np.zeros(2, dtype=fm.L2_DTYPE)
+    out = np.full((slots + 1) * slot, 0xA5, dtype=np.uint8)
+    flen = np.full(slots + 1, 0xCCCCCCCC, dtype=np.uint32)
+    st = np.full(2, 0xDEADBEEF, dtype=np.uint32)
+    p = lambda x: x.ctypes.data
+    assert L.ether_tx_frame_host(p(dgram), dgram.size, p(off), p(ln), p(l2), 2, 76, 1, p(out), slot, slots + 1, p(flen),
+                                 p(st)) == -errno.EINVAL
+    msg = L.fcs_last_error().decode()
+    assert "datagram 1:" in msg and "8185 slots" in msg and "host chunk" in msg
+    assert (out == 0xA5).all() and (flen == 0xCCCCCCCC).all() and (st == 0xDEADBEEF).all()
+
+
 def _no_gpu():
     try:
         import torch
