@@ -34,6 +34,11 @@
 #include "fcs_host_crc.hpp"
 #include "fcs_launch.hpp"
 #include "fcs_tables.hpp"
+#include "host_pipe.hpp"
+
+using hostpipe::ceil4;
+using hostpipe::DeviceGuard;
+using hostpipe::floor4;
 
 namespace {
 
@@ -58,28 +63,13 @@ int hip_fail(hipError_t e, const char *what) {
     return fail(err, "%s: %s", what, hipGetErrorString(e));
 }
 
+// This file's own HIPTRY, not host_pipe.hpp's: hip_fail above maps one more code and reports through fail.
+#undef HIPTRY
 #define HIPTRY(expr, what)                        \
     do {                                          \
         hipError_t e_ = (expr);                   \
         if (e_ != hipSuccess) return hip_fail(e_, what); \
     } while (0)
-
-// Makes `dev` current for the scope and restores the caller's device on exit (a host-batch call
-// must not leave a multi-GPU caller's thread on another device: its next *_dev call resolves the
-// device from the thread's current one).
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        err = hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
 
 // Drop-in ether_fcs health counters (fcs_engine_stats).
 std::atomic<uint64_t> g_dropin_calls{0}, g_dropin_retries{0}, g_dropin_recovered{0}, g_lane_resets{0};
@@ -359,9 +349,6 @@ int current_dev_state(DevState **out) {
     if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
     return dev_state(dev, out);
 }
-
-inline uint64_t floor4(uint64_t x) { return x & ~3ull; }
-inline uint64_t ceil4(uint64_t x) { return (x + 3) & ~3ull; }
 
 uint32_t segments(uint32_t len) { return len ? (len + fcs::kSegBytes - 1) / fcs::kSegBytes : 1u; }
 

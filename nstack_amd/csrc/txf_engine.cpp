@@ -1,47 +1,28 @@
 // txf_engine.cpp — the C ABI of include/nstack_txf.h around txf_kernel.hip.
 //
 // Device forms validate and launch. The host form plans on the host (txf_plan.hpp), checks every
-// datagram and the slot capacity, and then runs a double-buffered H2D -> kernel -> D2H pipeline over
-// datagram ranges on the engine's first GPU, in staging of its own (as txs_engine.cpp's run_host):
+// datagram and the slot capacity, and then runs the double-buffered H2D -> kernel -> D2H pipeline of
+// host_pipe.hpp over datagram ranges on the engine's first GPU, in staging and with a cut of its own:
 // a chunk's datagrams are gathered back to back, its frames come back slot by slot and only their
 // F (+ 4) bytes are copied into the caller's arena. No CPU path: a failure is returned, never
 // answered on the host, and the FCS engine's host-batch and fallback counters are not touched.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cerrno>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <vector>
 
 #include "../../include/nstack_txf.h"
 #include "fcs_device.hpp"
 #include "fcs_error.hpp"
+#include "host_pipe.hpp"
 #include "txf_launch.hpp"
 
 static_assert(sizeof(txf_l2) == 12, "the MAC record is 12 bytes");
 
+using namespace hostpipe;
+
 namespace {
-
-int hip_fail(hipError_t e, const char *what) {
-    const int err = (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorNoBinaryForGpu ||
-                     e == hipErrorInvalidDeviceFunction || e == hipErrorInvalidImage)
-                        ? ENODEV
-                        : (e == hipErrorOutOfMemory ? ENOMEM : EIO);
-    return fcs::set_error(err, "%s: %s", what, hipGetErrorString(e));
-}
-
-#define HIPTRY(expr, what)                                 \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_fail(e_, what);   \
-    } while (0)
-
-inline uint64_t floor4(uint64_t x) { return x & ~3ull; }
-inline uint64_t ceil4(uint64_t x) { return (x + 3) & ~3ull; }
 
 int check_call(uint32_t mtu, uint32_t flags) {
     if (flags & ~txf::kKnownFlags) return fcs::set_error(EINVAL, "unknown flag bits 0x%x", flags & ~txf::kKnownFlags);
@@ -69,14 +50,6 @@ int launch(txf::FParams &p, int dev, int cus, hipStream_t st) {
     });
 }
 
-int copy_name(const char *r, char *out, uint64_t cap) {
-    if (!out || cap == 0) return -EINVAL;
-    const uint64_t k = std::min<uint64_t>(std::strlen(r), cap - 1);
-    std::memcpy(out, r, k);
-    out[k] = 0;
-    return (int)k;
-}
-
 // ---- host pipeline ----
 constexpr uint64_t kInBytes = 32ull << 20;     // a chunk's datagrams
 constexpr uint64_t kOutBytes = 64ull << 20;    // a chunk's slots
@@ -86,79 +59,10 @@ constexpr uint64_t kChunkDgs = 1ull << 18;
 constexpr uint64_t kChunkFrames = 1ull << 20;
 constexpr int kDepth = 2;
 
-struct Slot {
-    uint8_t *d_in = nullptr, *h_in = nullptr;
-    uint64_t *d_off = nullptr, *h_off = nullptr;     // off[kChunkDgs], then first[kChunkDgs]
-    uint32_t *d_len = nullptr, *h_len = nullptr;
-    uint8_t *d_l2 = nullptr, *h_l2 = nullptr;
-    uint8_t *d_out = nullptr, *h_out = nullptr;
-    uint32_t *d_flen = nullptr, *h_flen = nullptr;
-    hipEvent_t done = nullptr;
-    bool live = false;
-    uint64_t k0 = 0, frames = 0;
-};
-
-struct HostPipe {
-    std::mutex mu;
-    int dev = -1, cus = 0;
-    hipStream_t stream = nullptr;
-    Slot slot[kDepth];
-};
-
-std::mutex g_pipes_mu;
-std::map<int, std::unique_ptr<HostPipe>> g_pipes;
-
-void free_pipe(HostPipe &hp) {
-    for (Slot &s : hp.slot) {
-        if (s.done) (void)hipEventDestroy(s.done);
-        for (void *d : {(void *)s.d_in, (void *)s.d_off, (void *)s.d_len, (void *)s.d_l2, (void *)s.d_out, (void *)s.d_flen})
-            if (d) (void)hipFree(d);
-        for (void *h : {(void *)s.h_in, (void *)s.h_off, (void *)s.h_len, (void *)s.h_l2, (void *)s.h_out, (void *)s.h_flen})
-            if (h) (void)hipHostFree(h);
-        s = Slot{};
-    }
-    if (hp.stream) (void)hipStreamDestroy(hp.stream);
-    hp.stream = nullptr;
-}
-
-int alloc_pipe(HostPipe &hp) {
-    HIPTRY(hipSetDevice(hp.dev), "hipSetDevice");
-    HIPTRY(hipStreamCreateWithFlags(&hp.stream, hipStreamNonBlocking), "hipStreamCreate");
-    for (Slot &s : hp.slot) {
-        HIPTRY(hipMalloc(&s.d_in, kInBytes + 64), "hipMalloc(txf staging)");
-        HIPTRY(hipHostMalloc(&s.h_in, kInBytes + 64, hipHostMallocDefault), "hipHostMalloc(txf staging)");
-        HIPTRY(hipMalloc(&s.d_off, kChunkDgs * 16), "hipMalloc(off)");
-        HIPTRY(hipHostMalloc(&s.h_off, kChunkDgs * 16, hipHostMallocDefault), "hipHostMalloc(off)");
-        HIPTRY(hipMalloc(&s.d_len, kChunkDgs * 4), "hipMalloc(len)");
-        HIPTRY(hipHostMalloc(&s.h_len, kChunkDgs * 4, hipHostMallocDefault), "hipHostMalloc(len)");
-        HIPTRY(hipMalloc(&s.d_l2, kChunkDgs * 12), "hipMalloc(l2)");
-        HIPTRY(hipHostMalloc(&s.h_l2, kChunkDgs * 12, hipHostMallocDefault), "hipHostMalloc(l2)");
-        HIPTRY(hipMalloc(&s.d_out, kOutBytes), "hipMalloc(txf frames)");
-        HIPTRY(hipHostMalloc(&s.h_out, kOutBytes, hipHostMallocDefault), "hipHostMalloc(txf frames)");
-        HIPTRY(hipMalloc(&s.d_flen, kChunkFrames * 4), "hipMalloc(flen)");
-        HIPTRY(hipHostMalloc(&s.h_flen, kChunkFrames * 4, hipHostMallocDefault), "hipHostMalloc(flen)");
-        HIPTRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "hipEventCreate");
-    }
-    return 0;
-}
-
-int get_pipe(int dev, int cus, HostPipe **out) {
-    std::lock_guard<std::mutex> lk(g_pipes_mu);
-    auto &up = g_pipes[dev];
-    if (!up) {
-        auto hp = std::make_unique<HostPipe>();
-        hp->dev = dev;
-        hp->cus = cus;
-        const int rc = alloc_pipe(*hp);
-        if (rc) {   // a half-built pipeline holds nothing: the next call starts over
-            free_pipe(*hp);
-            return rc;
-        }
-        up = std::move(hp);
-    }
-    *out = up.get();
-    return 0;
-}
+struct TxfPipe;   // names this engine's pipelines (host_pipe.hpp)
+enum { kIn, kOff, kLen, kL2, kOut, kFlen };   // kOff: off[kChunkDgs], then first[kChunkDgs]
+const std::vector<BufSpec> kBufs = {{kInBytes + 64, "txf staging"}, {kChunkDgs * 16, "off"},   {kChunkDgs * 4, "len"},
+                                    {kChunkDgs * 12, "l2"},         {kOutBytes, "txf frames"}, {kChunkFrames * 4, "flen"}};
 
 // first[0..n] is the host plan; frames of datagrams [i, e) go to slots [first[i], first[e]).
 int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len, const uint8_t *l2, uint64_t n,
@@ -166,34 +70,13 @@ int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len,
     int dev = 0, cus = 0;
     int rc = fcs::engine_device0(&dev, &cus);
     if (rc) return rc;
-    HostPipe *hp = nullptr;
-    if ((rc = get_pipe(dev, cus, &hp))) return rc;
-    std::lock_guard<std::mutex> lk(hp->mu);
-    int cur = 0;
-    HIPTRY(hipGetDevice(&cur), "hipGetDevice");
-    HIPTRY(hipSetDevice(dev), "hipSetDevice");
-    const uint32_t *blob = nullptr;
-    if ((flags & txf::kFlagFcs) && (rc = fcs::device_tables(dev, &blob))) return rc;
     const uint64_t T = (flags & txf::kFlagFcs) ? 4 : 0;
-    auto drain = [&](Slot &s) -> int {
-        if (!s.live) return 0;
-        HIPTRY(hipEventSynchronize(s.done), "hipEventSynchronize");
-        for (uint64_t q = 0; q < s.frames; q++) {
-            const uint32_t F = s.h_flen[q];
-            std::memcpy(out + (s.k0 + q) * slot, s.h_out + q * slot, F + T);
-            if (flen) flen[s.k0 + q] = F;
-        }
-        s.live = false;
-        return 0;
-    };
-    uint64_t i = 0;
-    int b = 0;
-    auto step = [&]() -> int {
-        Slot &s = hp->slot[b];
-        int rc = drain(s);
+    // a refused datagram travels as an empty one: its status is the host plan's
+    auto glen = [&](uint64_t q) -> uint32_t { return first[q + 1] > first[q] ? len[q] : 0u; };
+    auto issue = [&](Slot &s, hipStream_t st, uint64_t i) -> int64_t {
+        const uint32_t *blob = nullptr;
+        int rc = (flags & txf::kFlagFcs) ? fcs::device_tables(dev, &blob) : 0;
         if (rc) return rc;
-        // a refused datagram travels as an empty one: its status is the host plan's
-        auto glen = [&](uint64_t q) -> uint32_t { return first[q + 1] > first[q] ? len[q] : 0u; };
         uint64_t e = i, sum = 0;
         while (e < n && e - i < kChunkDgs && sum + glen(e) <= kInBytes && first[e + 1] - first[i] <= kChunkFrames &&
                (first[e + 1] - first[i]) * slot <= kOutBytes) {
@@ -203,62 +86,56 @@ int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len,
         if (e == i)   // checked before any work (ether_tx_frame_host): cannot happen
             return fcs::set_error(EINVAL, "datagram %llu exceeds the host chunk", (unsigned long long)i);
         const uint64_t np = e - i, frames = first[e] - first[i];
-        uint64_t w = 0;
+        if (!frames) return (int64_t)e;   // a chunk of refused datagrams needs no device
+        uint8_t *h_in = s.h<uint8_t>(kIn);
+        uint64_t *h_off = s.h<uint64_t>(kOff), *d_off = s.d<uint64_t>(kOff), w = 0;
         for (uint64_t q = 0; q < np; q++) {
             const uint32_t gl = glen(i + q);
-            std::memcpy(s.h_in + w, dgram + off[i + q], gl);
-            s.h_off[q] = w;
-            s.h_off[kChunkDgs + q] = first[i + q] - first[i];
-            s.h_len[q] = gl;
+            std::memcpy(h_in + w, dgram + off[i + q], gl);
+            h_off[q] = w;
+            h_off[kChunkDgs + q] = first[i + q] - first[i];
+            s.h<uint32_t>(kLen)[q] = gl;
             w += gl;
         }
         const uint64_t nl2 = (flags & txf::kFlagL2One) ? 1 : np;
-        std::memcpy(s.h_l2, l2 + ((flags & txf::kFlagL2One) ? 0 : i * 12), nl2 * 12);
-        hipStream_t st = hp->stream;
-        if (frames) {   // a chunk of refused datagrams needs no device
-            if (w) HIPTRY(hipMemcpyAsync(s.d_in, s.h_in, w, hipMemcpyHostToDevice, st), "H2D datagrams");
-            HIPTRY(hipMemcpyAsync(s.d_off, s.h_off, np * 8, hipMemcpyHostToDevice, st), "H2D off");
-            HIPTRY(hipMemcpyAsync(s.d_off + kChunkDgs, s.h_off + kChunkDgs, np * 8, hipMemcpyHostToDevice, st), "H2D first");
-            HIPTRY(hipMemcpyAsync(s.d_len, s.h_len, np * 4, hipMemcpyHostToDevice, st), "H2D len");
-            HIPTRY(hipMemcpyAsync(s.d_l2, s.h_l2, nl2 * 12, hipMemcpyHostToDevice, st), "H2D l2");
-            txf::FParams p{};
-            p.dg = (uint64_t)s.d_in;
-            p.lo4 = floor4(p.dg);
-            p.hi4 = ceil4(p.dg + kInBytes + 64);   // the staging buffer
-            p.off = s.d_off;
-            p.len = s.d_len;
-            p.n = np;
-            p.mtu = mtu;
-            p.flags = flags;
-            p.l2 = s.d_l2;
-            p.first = s.d_off + kChunkDgs;
-            p.out = (uint64_t)s.d_out;
-            p.slot = slot;
-            p.slots = frames;
-            p.flen = s.d_flen;
-            p.blob = blob;
-            if ((rc = launch(p, hp->dev, cus, st))) return rc;
-            HIPTRY(hipMemcpyAsync(s.h_out, s.d_out, frames * slot, hipMemcpyDeviceToHost, st), "D2H frames");
-            HIPTRY(hipMemcpyAsync(s.h_flen, s.d_flen, frames * 4, hipMemcpyDeviceToHost, st), "D2H flen");
-            HIPTRY(hipEventRecord(s.done, st), "hipEventRecord");
-            s.live = true;
-            s.k0 = first[i];
-            s.frames = frames;
-        }
-        i = e;
-        b = (b + 1) % kDepth;
-        return 0;
+        std::memcpy(s.h<void>(kL2), l2 + ((flags & txf::kFlagL2One) ? 0 : i * 12), nl2 * 12);
+        if (w) HIPTRY(hipMemcpyAsync(s.d<void>(kIn), h_in, w, hipMemcpyHostToDevice, st), "H2D datagrams");
+        HIPTRY(hipMemcpyAsync(d_off, h_off, np * 8, hipMemcpyHostToDevice, st), "H2D off");
+        HIPTRY(hipMemcpyAsync(d_off + kChunkDgs, h_off + kChunkDgs, np * 8, hipMemcpyHostToDevice, st), "H2D first");
+        HIPTRY(hipMemcpyAsync(s.d<void>(kLen), s.h<void>(kLen), np * 4, hipMemcpyHostToDevice, st), "H2D len");
+        HIPTRY(hipMemcpyAsync(s.d<void>(kL2), s.h<void>(kL2), nl2 * 12, hipMemcpyHostToDevice, st), "H2D l2");
+        txf::FParams p{};
+        p.dg = (uint64_t)s.d<void>(kIn);
+        p.lo4 = floor4(p.dg);
+        p.hi4 = ceil4(p.dg + kInBytes + 64);   // the staging buffer
+        p.off = d_off;
+        p.len = s.d<uint32_t>(kLen);
+        p.n = np;
+        p.mtu = mtu;
+        p.flags = flags;
+        p.l2 = s.d<uint8_t>(kL2);
+        p.first = d_off + kChunkDgs;
+        p.out = (uint64_t)s.d<void>(kOut);
+        p.slot = slot;
+        p.slots = frames;
+        p.flen = s.d<uint32_t>(kFlen);
+        p.blob = blob;
+        if ((rc = launch(p, dev, cus, st))) return rc;
+        HIPTRY(hipMemcpyAsync(s.h<void>(kOut), s.d<void>(kOut), frames * slot, hipMemcpyDeviceToHost, st), "D2H frames");
+        HIPTRY(hipMemcpyAsync(s.h<void>(kFlen), s.d<void>(kFlen), frames * 4, hipMemcpyDeviceToHost, st), "D2H flen");
+        s.i0 = first[i];   // the chunk's first slot and its frames
+        s.n = frames;
+        s.live = true;
+        return (int64_t)e;
     };
-    while (i < n && !rc) rc = step();
-    if (rc) {   // never leave a slot that would later be drained into this call's arena
-        (void)hipStreamSynchronize(hp->stream);
-        for (Slot &s : hp->slot) s.live = false;
-    }
-    for (Slot &s : hp->slot) {
-        const int r2 = drain(s);
-        if (!rc) rc = r2;
-    }
-    hipSetDevice(cur);
+    auto drain = [&](Slot &s) {
+        for (uint64_t q = 0; q < s.n; q++) {
+            const uint32_t F = s.h<uint32_t>(kFlen)[q];
+            std::memcpy(out + (s.i0 + q) * slot, s.h<uint8_t>(kOut) + q * slot, F + T);
+            if (flen) flen[s.i0 + q] = F;
+        }
+    };
+    rc = run_pipe<TxfPipe>(dev, kDepth, kBufs, n, issue, drain);
     return rc ? (int64_t)rc : (int64_t)first[n];
 }
 

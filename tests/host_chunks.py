@@ -1,9 +1,10 @@
 """The chunker of the host forms inet_csum_batch_host, ether_rx_validate_host and ether_tx_seal_host
-restated: the three engines' run_host loops cut a batch into chunks by the same three bounds
-(packets, bytes, and the span rule) and stage each chunk densely or gathered. `host_chunks` is the
-vectorised restatement the GPU tests assert their layouts with, `host_chunks_scalar` the literal
-transcription of the C++ loop it is checked against (tests/test_host_chunks_model.py). Test
-infrastructure only."""
+restated: the three engines cut a batch into chunks with one C++ function (hostchunk::cut in
+nstack_amd/csrc/host_chunk.hpp: the packet bound, the byte bound and the span rule) and stage each
+chunk densely or gathered. `host_chunks` is the vectorised restatement the GPU tests assert their
+layouts with, `host_chunks_scalar` the literal transcription of the C++ loop; tests/test_host_chunks_model.py
+holds the first to the second, and the second to the C++ function itself, run stand-alone by
+tests/c/host_chunk_check.cpp. Test infrastructure only."""
 import os
 import re
 
@@ -37,7 +38,7 @@ def _kind(span, K):
 
 
 def host_chunks_scalar(off, ln, K, P, T):
-    """The while loop of run_host, line by line: [(i, e, bound, staging, sum, span)]."""
+    """The while loop of hostchunk::cut, line by line: [(i, e, bound, staging, sum, span)]."""
     off, ln = [int(x) for x in off], [int(x) for x in ln]
     n, i, out = len(off), 0, []
     while i < n:
@@ -67,7 +68,7 @@ def host_chunks_scalar(off, ln, K, P, T):
 
 
 def host_chunks(off, ln, K, P, T):
-    """The chunks run_host forms from off[] and len[]: [(i, e, bound, staging, sum, span)], frames
+    """The chunks the host forms make of off[] and len[]: [(i, e, bound, staging, sum, span)], frames
     [i, e); `bound` is what refused frame e ("pkts", "bytes", "span"; "bytes" where both of the last
     two would, since the loop tests it first) or "end"; `staging` is "dense" (one span copy) or
     "gather"; T = 4 for the sealer with TXS_F_FCS (every frame counts with its FCS place), else 0.

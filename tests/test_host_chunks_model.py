@@ -1,6 +1,11 @@
 """CPU check of tests/host_chunks.py: the vectorised chunker equals the literal transcription of the
-engines' run_host loop on a few thousand random layouts at small bounds, and the three engines'
-constants are the ones the layouts of tests/test_gpu_host_chunks.py were sized for."""
+engines' chunker on a few thousand random layouts at small bounds, the transcription equals the
+chunker itself (nstack_amd/csrc/host_chunk.hpp, run stand-alone under the sanitizers by
+tests/c/host_chunk_check.cpp) on the same layouts, and the three engines' constants are the ones the
+layouts of tests/test_gpu_host_chunks.py were sized for."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -79,6 +84,54 @@ def test_bytes_bound_is_reported_where_the_span_rule_would_stop_too():
     ln = np.array([1000, 1000, 1000], dtype=np.uint32)
     for f in (hc.host_chunks, hc.host_chunks_scalar):
         assert f(off, ln, K, P, 4) == [(0, 3, "end", "gather", 3012, 11004)]
+
+
+# ---- the C++ chunker itself (a stand-alone program: nothing is loaded into Python) ----
+HAND_MADE = (([0, 1600, 3200], [1500, 1500, 1500], 0), ([0, 3000, 6000], [1500, 1500, 1500], 0),
+             ([0, 5000, 10000], [1000, 1000, 1000], 4))   # test_bytes_bound_is_reported_where_...'s three
+
+
+def _layouts(T):
+    """The 1800 layouts of test_vectorised_chunker_equals_the_transcribed_loop for this T, then the
+    hand-made ones with this T: [(off, len)]."""
+    rng = np.random.default_rng(2024 + T)
+    out = [layout(KINDS[t % len(KINDS)], rng, T) for t in range(1800)]
+    return out + [(np.array(o, dtype=np.uint64), np.array(l, dtype=np.uint32)) for o, l, t in HAND_MADE if t == T]
+
+
+@pytest.fixture(scope="module")
+def check_program():
+    cdir = os.path.join(hc.ROOT, "tests", "c")
+    subprocess.run(["make", "-s", "-C", cdir, "-f", "host_chunk_check.mk"], check=True)
+    return os.path.join(cdir, "host_chunk_check")
+
+
+@pytest.mark.parametrize("T", [0, 4])
+def test_the_cxx_chunker_equals_the_transcribed_loop(check_program, T):
+    lays = _layouts(T)
+    text = "".join(f"{K} {P} {T} {len(off)}\n{' '.join(map(str, off))}\n{' '.join(map(str, ln))}\n" for off, ln in lays)
+    r = subprocess.run([check_program], input=text, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    got = [blk.split("\n") for blk in r.stdout.split("end\n")]
+    assert got.pop() == [""] and len(got) == len(lays)
+    seen, refused = set(), 0
+    for t, ((off, ln), lines) in enumerate(zip(lays, got)):
+        assert lines.pop() == ""
+        try:
+            want = hc.host_chunks_scalar(off, ln, K, P, T)
+        except hc.FrameTooLong as e:
+            assert lines[-1] == f"toolong {e.index}", (t, lines[-1])
+            refused += 1
+            continue
+        assert not any(x.startswith("toolong") for x in lines), t
+        rows = [x.split() for x in lines]
+        # (i, e, staging, sum, hi - lo) of every chunk
+        assert [(int(x[0]), int(x[1]), x[5], int(x[2]), int(x[4]) - int(x[3])) for x in rows] == \
+            [(i, e, staging, total, span) for i, e, _, staging, total, span in want], t
+        seen |= {(bound, staging) for _, _, bound, staging, _, _ in want}
+    assert refused == 1800 // len(KINDS)
+    assert seen == {(b, s) for b in ("pkts", "bytes", "span", "end") for s in ("dense", "gather")}, seen
 
 
 def test_engine_constants_are_the_ones_the_layouts_assume():
