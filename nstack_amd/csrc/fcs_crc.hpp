@@ -1,6 +1,8 @@
-// fcs_crc.hpp — device helpers of the CRC kernels shared by fcs_kernel.hip and rxv_kernel.hip:
-// table staging, the slice-by-4 step, the shift tables' readers, the 16-lane XOR and the per-wave
-// failing-frame counters. Device code only (included by the .hip translation units).
+// fcs_crc.hpp — device helpers of the CRC kernels shared by fcs_kernel.hip and the frame-walk
+// kernels (rxv_kernel.hip, txs_kernel.hip, txf_kernel.hip): table staging, the slice-by-4 step, the
+// shift tables' readers, a chunk's two chains and INV start, the LDS-DMA lane constants and window
+// chains, the 16-lane XOR and the per-wave failing-frame counters. Device code only (included by
+// the .hip translation units).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,6 +112,27 @@ __device__ __forceinline__ uint32_t uniform_shift(const uint8_t *lds, uint32_t s
         r[t] = lds_rd(lds, ((sh & 0x3Cu) | REGION) + t * 64);
     }
     return xor9(r, extra);
+}
+
+// Two independent 12-word chains over a chunk, merged with A_48 (fcs_kernel.hip's chunk_value
+// without its measurement switches): the chunk's CRC register from start value x0.
+__device__ __forceinline__ uint32_t chunk_crc(const uint8_t *lds, const uint32_t (&w)[kChunkWords], uint32_t x0,
+                                              uint32_t tb0, uint32_t tb1) {
+    uint32_t xa = x0 ^ w[0], xb = w[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        xa = step4(lds, xa, i < 11 ? w[i + 1] : 0u, tb0, tb1);
+        xb = step4(lds, xb, i < 11 ? w[13 + i] : 0u, tb0, tb1);
+    }
+    return uniform_shift<kLdsH48>(lds, xa, xb);
+}
+
+// The INV start of a frame's first chunk: zr bytes from chunk start to frame start; 0 for a lane
+// whose chunk does not hold the frame start.
+__device__ __forceinline__ uint32_t inv_start(const uint8_t *lds, int zr) {
+    const int zi = zr < 0 ? 0 : (zr > kChunkBytes - 1 ? kChunkBytes - 1 : zr);
+    const uint32_t iv = lds_rd(lds, kLdsInv + 4u * (uint32_t)zi);
+    return (zr >= 0 && zr < kChunkBytes) ? iv : 0u;
 }
 
 // XOR over each 16-lane row (one frame); every lane of the row ends with the row's XOR.
@@ -247,6 +270,47 @@ __device__ __forceinline__ uint32_t merge_shift_dma(const uint8_t *lds, int m, u
         r[t] = lds_rd(lds, (sh & 0x3Cu) | base);
     }
     return xor9(r, extra);
+}
+
+// The per-lane constants of the LDS-DMA lookups, formed from a lane number (rxv_dma_kernel forms
+// them once, txs_dma_kernel per item from an opaque lane number: DESIGN.md §3.10 "Registers").
+struct DmaLane {
+    uint32_t B[4], SEL[4];   // step4_l8's bases and selectors
+    uint32_t lanebase;       // lane_shift_dma's
+};
+
+__device__ __forceinline__ DmaLane dma_lane(uint32_t ln) {
+    const uint32_t h = (ln >> 3) & 3u, r4 = (ln & 7u) * 4u;
+    return DmaLane{{r4 + 32u * (0u ^ h), r4 + 32u * (1u ^ h), r4 + 32u * (2u ^ h), r4 + 32u * (3u ^ h)},
+                   {0x0C0C0400u + ((0u ^ h) << 8), 0x0C0C0400u + ((1u ^ h) << 8), 0x0C0C0400u + ((2u ^ h) << 8),
+                    0x0C0C0400u + ((3u ^ h) << 8)},
+                   kDmaHole + (ln & 31u) * 4u};
+}
+
+// The INV start of a frame's front lane (15 of its row), whose window has zc leading bytes; 0 for the others.
+__device__ __forceinline__ uint32_t dma_inv_start(const uint8_t *lds, uint32_t ln, int zc) {
+    return (ln & 15u) == (uint32_t)(kGroup - 1)
+               ? lds_rd(lds, dma_hole(kDmaInvHole + (uint32_t)zc / 32u) + (uint32_t)(zc % 32) * 4u)
+               : 0u;
+}
+
+// kDmaChains independent chains over a lane window, merged, shifted to the frame end by the lane's
+// own table: the lane's share of the frame's CRC register (row_xor joins them).
+__device__ __forceinline__ uint32_t dma_chunk_crc(const uint8_t *lds, const uint32_t (&w)[kChunkWords], uint32_t x0,
+                                                  const uint32_t (&B)[4], const uint32_t (&SEL)[4], uint32_t lanebase) {
+    constexpr int CL = kDmaChainWords;
+    uint32_t xs[kDmaChains];
+#pragma unroll
+    for (int hh = 0; hh < kDmaChains; hh++) xs[hh] = w[hh * CL] ^ (hh == 0 ? x0 : 0u);
+#pragma unroll
+    for (int i = 0; i < CL; i++)
+#pragma unroll
+        for (int hh = 0; hh < kDmaChains; hh++)
+            xs[hh] = step4_l8(lds, xs[hh], i < CL - 1 ? w[hh * CL + i + 1] : 0u, B, SEL);
+    uint32_t mv = xs[kDmaChains - 1];
+#pragma unroll
+    for (int hh = 0; hh < kDmaChains - 1; hh++) mv = merge_shift_dma(lds, kDmaChains - 2 - hh, xs[hh], mv);
+    return lane_shift_dma(lds, mv, lanebase);
 }
 
 // The slot DMA: six 1 KiB rows from two address registers. The instruction's offset (13-bit,

@@ -1503,12 +1503,6 @@ __device__ __forceinline__ uint32_t chunk_value(const uint8_t *lds, const Chunk 
     return uniform_shift<kLdsH48>(lds, xa, xb);
 }
 
-__device__ __forceinline__ uint32_t inv_start(const uint8_t *lds, int zr) {
-    const int zi = zr < 0 ? 0 : (zr > kChunkBytes - 1 ? kChunkBytes - 1 : zr);
-    const uint32_t iv = lds_rd(lds, kLdsInv + 4u * (uint32_t)zi);
-    return (zr >= 0 && zr < kChunkBytes) ? iv : 0u;
-}
-
 __device__ __forceinline__ int clamp_zr(int64_t z) {
     return z < -1 ? -1 : (z > kChunkBytes ? kChunkBytes : (int)z);
 }

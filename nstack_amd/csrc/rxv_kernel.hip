@@ -39,24 +39,95 @@
 
 #include <atomic>
 
-#include "dispenser.hpp"
 #include "fcs_crc.hpp"
 #include "fcs_tables.hpp"
+#include "frame_walk.hpp"
 #include "rxv_launch.hpp"
-#include "rxv_parts.hpp"
 
 namespace rxv {
+
+// What a frame's header decided before its first chunk is summed (uniform over the frame's lanes).
+struct Hdr {
+    uint32_t bits;    // verdict bits that need no sum
+    uint32_t ps;      // L4: accumulator start plus pseudo header; 0 = no L4 checksum to verify
+    int cl;           // frame position of the first byte behind the L4 segment (tail mask)
+    uint32_t sums;    // this lane's header_sums
+};
+
+template <bool TRAILER>
+__device__ __forceinline__ Hdr decode(const Frame &fr, const Chunk &ch, int j) {
+    Hdr h{0u, 0u, 0, 0u};
+    const uint32_t F = fr.len, T = TRAILER ? 4u : 0u, r = (uint32_t)fr.start & 3u;
+    const HdrWords hw = header_words(fr, ch);
+    const uint32_t w12 = hw.w12, src = hw.src, dst = hw.dst;
+    const uint32_t hlen = hw.hlen, iplen = hw.iplen, foff = hw.foff, proto = hw.proto;
+    // the UDP checksum field, frame bytes 20 + hlen and the next (a multiple of 4: dword (20 + hlen) / 4)
+    const uint32_t ud = (20u + hlen) >> 2;   // 5..20
+    const uint32_t ua0 = row_get(ch.h0, ud & 15u), ua1 = row_get(ch.h1, ud & 15u);
+    const uint32_t ub0 = row_get(ch.h0, (ud + 1u) & 15u), ub1 = row_get(ch.h1, (ud + 1u) & 15u);
+    const uint32_t ufield =
+        __builtin_amdgcn_alignbyte(ud + 1u < 16u ? ub0 : ub1, ud < 16u ? ua0 : ua1, r) & 0xffffu;
+
+    int che = 0;   // frame position behind the IP header; 0 = no header sum
+    if (F < 14u + T) {
+        h.bits = kRunt;
+    } else if (swap16(w12 & 0xffffu) == 0x0800u) {
+        const uint32_t P = F - 14u - T;
+        h.bits = kIpv4;
+        if (bad_ip_header(hw, P)) {
+            h.bits |= kIpBadHdr;
+        } else {
+            che = 14 + (int)hlen;
+            h.bits |= proto << kProtoShift;
+            if (iplen != P) h.bits |= kIpBadLen;
+            if (foff & 0x3fffu) {
+                h.bits |= kFrag;
+            } else if (hlen <= iplen && iplen <= P) {
+                const uint32_t L = iplen - hlen, l16 = swap16(L);
+                const uint32_t a4 = (src & 0xffffu) + (src >> 16) + (dst & 0xffffu) + (dst >> 16);
+                if (proto == 6u) {          // tcp_checksum(ntohl(src), ntohl(dst), seg, L): htonl() of both
+                    if (L < 20u) h.bits |= kL4Short;   // gives back the words as they lie in the header
+                    else h.ps = 0xffffu + a4 + 0x0600u + l16;
+                } else if (proto == 17u) {  // udp_checksum(seg, L, src, dst): the raw in_addr_t words
+                    if (L < 8u) h.bits |= kL4Short;
+                    else if (ufield != 0u) h.ps = a4 + 0x1100u + l16;
+                } else if (proto == 1u) {   // ip_checksum(msg, L)
+                    if (L < 4u) h.bits |= kL4Short;
+                    else h.ps = 0xffffu;
+                }
+                if (h.ps) {
+                    h.bits |= kL4Checked;
+                    h.cl = 14 + (int)iplen;
+                }
+            }
+        }
+    }
+    h.sums = header_sums(ch, j, r, che);
+    return h;
+}
+
+// The verdict's checksum bits, from the reduced sums (row-uniform): every check is "the reference
+// function returns non-zero".
+__device__ __forceinline__ uint32_t sum_verdict(uint32_t v, const Hdr &H, uint64_t tot, uint64_t tail, bool odd_len,
+                                                bool odd_start) {
+    const Sums z = reduce_sums(tot, tail, H.sums, odd_len, odd_start);
+    if ((v & (kIpv4 | kIpBadHdr)) == kIpv4 && fold64(0xffffull + z.hdr_s) != 0xffffu) v |= kIpBadCsum;
+    // the common case, said so: without the hint both checks were laid out of line in rxv_kernel (a
+    // jump out and back per frame; IMIX with the CRC 34.17 against 33.44 ms, with it 33.30 against
+    // 33.92). rxv_dma_kernel shares the function; its rows measure the same with the hint as before.
+    if (__builtin_expect(H.ps != 0u, 1)) {
+        const uint64_t l4 = (uint64_t)H.ps + z.tot_s + (0xffffu - z.head_s) + (0xffffu - z.tail_s);
+        if (fold64(l4) != 0xffffu) v |= kL4BadCsum;
+    }
+    return v;
+}
 
 template <bool VAR, bool TRAILER, bool TINY, int NT>
 __global__ __launch_bounds__(NT, 1) void rxv_kernel(RParams p) {
     // without the CRC only the per-wave bad counters live in LDS
     constexpr uint32_t kBad = TRAILER ? fcs::kLdsBad : 0u;
     __shared__ __attribute__((aligned(16))) uint8_t lds[TRAILER ? fcs::kLdsBytes : 16 * 8];
-    if (TRAILER) {
-        fcs::KParams kp{};
-        kp.blob = p.blob;
-        fcs::stage_tables<NT>(kp, lds);
-    }
+    if (TRAILER) fcs::stage_tables<NT>(tables_of(p.blob), lds);
     fcs::init_bad<kBad>(lds);
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
     uint32_t tb0, tb1;
@@ -64,37 +135,14 @@ __global__ __launch_bounds__(NT, 1) void rxv_kernel(RParams p) {
     const uint32_t lanebase = fcs::kLdsLane | ((uint32_t)(lane & 31) * 4u);
     const uint64_t Q = (uint64_t)gridDim.x * (NT / kGroup);   // frame slots in the grid
 
-    auto next = [&](const Pos &c) -> Pos {
-        Pos n = c;
-        n.k = c.k + 1;
-        if (n.k >= c.fr.m) {
-            n.f = c.f + Q;
-            n.k = 0;
-        }
-        n.act = c.act && n.f < p.n;
-        if (n.act && n.k == 0) n.fr = frame_of<VAR>(p, n.f);
-        return n;
-    };
-
     // per-frame state, carried over the frame's segments
     uint32_t s = 0;            // CRC register
     uint64_t tot = 0, tail = 0;
     Hdr H{0u, 0u, 0, 0u};
 
     auto process = [&](const Pos &c, const Chunk &ch) {
-        uint32_t d[kChunkWords + 1];
-#pragma unroll
-        for (int q = 0; q < 6; q++) {
-            d[4 * q] = ch.x[q].x;
-            d[4 * q + 1] = ch.x[q].y;
-            d[4 * q + 2] = ch.x[q].z;
-            d[4 * q + 3] = ch.x[q].w;
-        }
-        d[kChunkWords] = ch.x6;
-        if (!TINY && __any(ch.dlead)) fcs::shift_up(d, ch.dlead);   // arena start only; uniform
         uint32_t w[kChunkWords];
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], ch.r);
+        chunk_words<TINY>(ch, w);
         const bool first = c.k == 0;
         if (__any(first)) {   // a frame's first chunk: its header fields
             const Hdr hn = decode<TRAILER>(c.fr, ch, j);
@@ -104,103 +152,29 @@ __global__ __launch_bounds__(NT, 1) void rxv_kernel(RParams p) {
                 tot = tail = 0;
             }
         }
-        if (first) {   // the front mask
-#pragma unroll
-            for (int i = 0; i < kChunkWords; i++) {
-                if (4 * i < (int)p.zmax) {   // uniform bound: words no front lane can mask are skipped
-                    int t = ch.zr - 4 * i;
-                    t = t < 0 ? 0 : (t > 4 ? 4 : t);
-                    w[i] &= (uint32_t)(0xFFFFFFFFull << (8 * t));
-                }
-            }
-        }
-        // ---- sums: every word into the total; words holding bytes from cl on also into the tail ----
-        {
-            uint64_t a = 0;
-#pragma unroll
-            for (int i = 0; i < kChunkWords; i += 2) a += (uint64_t)w[i] + w[i + 1];
-            tot += a;
-            // frame position of this chunk's first byte, and cl relative to it (clamped: the masks
-            // clamp again, this keeps the arithmetic inside an int)
-            const int64_t rel = (int64_t)c.fr.len - (int64_t)kSegBytes * (int64_t)(c.fr.m - 1 - c.k) -
-                                (int64_t)kChunkBytes * (j + 1);
-            const int64_t dl = (int64_t)H.cl - rel;
-            const int dt = !H.ps ? kChunkBytes + 4 : (dl < -4 ? -4 : (dl > kChunkBytes + 4 ? kChunkBytes + 4 : (int)dl));
-            uint64_t b = 0;
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                if (__any(dt < 24 * (blk + 1))) {
-#pragma unroll
-                    for (int i = 6 * blk; i < 6 * blk + 6; i++) b += fcs::clear_low_bits(w[i], 8 * (dt - 4 * i));
-                }
-            }
-            tail += b;
-        }
-        // ---- CRC: two independent 12-word chains, merged with A_48 (fcs_kernel.hip) ----
-        if (TRAILER) {
-            uint32_t x0 = 0;
-            if (first) {
-                const int zi = ch.zr < 0 ? 0 : (ch.zr > kChunkBytes - 1 ? kChunkBytes - 1 : ch.zr);
-                const uint32_t iv = fcs::lds_rd(lds, fcs::kLdsInv + 4u * (uint32_t)zi);
-                x0 = (ch.zr >= 0 && ch.zr < kChunkBytes) ? iv : 0u;
-            }
-            uint32_t xa = x0 ^ w[0], xb = w[12];
-#pragma unroll
-            for (int i = 0; i < 12; i++) {
-                xa = fcs::step4(lds, xa, i < 11 ? w[i + 1] : 0u, tb0, tb1);
-                xb = fcs::step4(lds, xb, i < 11 ? w[13 + i] : 0u, tb0, tb1);
-            }
-            const uint32_t rr = fcs::uniform_shift<fcs::kLdsH48>(lds, xa, xb);
-            s = first ? rr : fcs::uniform_shift<fcs::kLdsJump>(lds, s, rr);
-        }
+        if (first) front_mask(w, ch.zr, (int)p.zmax);
+        add_sums(w, rel_of(c.fr.len, c.fr.m, c.k, j), H.cl, H.ps, tot, tail);
+        if (TRAILER) s = crc_step(lds, s, w, first, ch.zr, tb0, tb1);
         // ---- the frame's last chunk: join the lanes, assemble the verdict ----
         const bool last = c.act && c.k + 1 == c.fr.m;
         if (__any(last)) {
             uint32_t v = H.bits;
             if (TRAILER) {
-                uint32_t x = last ? fcs::lane_shift(lds, s, lanebase) : 0u;
-                x = fcs::row_xor(x);
+                const uint32_t x = crc_join(lds, s, last, lanebase);
                 if ((c.fr.len ? ~x : 0u) != fcs::kResidue) v |= kFcsBad;
             }
-            const uint32_t te = fold64(row_sum(fold64(tot))), ta = fold64(row_sum(fold64(tail)));
-            const uint32_t hm = fold64(row_sum(H.sums & 0xffffu)), h0 = fold64(row_sum(H.sums >> 16));
-            // to the frame start's word grid: the end grid differs for an odd length, memory's for an odd start
-            const bool oe = c.fr.len & 1u, om = c.fr.start & 1ull;
-            const uint32_t tot_s = oe ? swap16(te) : te, tail_s = oe ? swap16(ta) : ta;
-            const uint32_t hdr_s = om ? swap16(hm) : hm, head_s = om ? swap16(h0) : h0;
-            if ((v & (kIpv4 | kIpBadHdr)) == kIpv4 && fold64(0xffffull + hdr_s) != 0xffffu) v |= kIpBadCsum;
-            if (H.ps) {
-                const uint64_t l4 = (uint64_t)H.ps + tot_s + (0xffffu - head_s) + (0xffffu - tail_s);
-                if (fold64(l4) != 0xffffu) v |= kL4BadCsum;
-            }
+            v = sum_verdict(v, H, tot, tail, c.fr.len & 1u, c.fr.start & 1ull);
             const bool st = last && j == 15;
             if (st) p.verdict[c.f] = v;
-            const uint64_t mb = __ballot(st && (v & p.bad_mask) != 0u);
-            if (mb != 0 && lane == 0) *fcs::wave_bad<kBad>(lds) += (uint64_t)__popcll(mb);
+            count_bad(fcs::wave_bad<kBad>(lds), lane, st && (v & p.bad_mask) != 0u);
         }
     };
 
-    Pos A, B;
-    A.f = (uint64_t)blockIdx.x * (NT / kGroup) + threadIdx.x / kGroup;
-    A.k = 0;
-    A.act = A.f < p.n;
-    A.fr = A.act ? frame_of<VAR>(p, A.f) : Frame{0, 0, 1};
-    Chunk CA, CB;
-    issue<TINY>(p, A, j, CA);
-    // two items in flight per lane: process one while the other's loads are outstanding
-    while (__any(A.act)) {
-        B = next(A);
-        issue<TINY>(p, B, j, CB);
-        process(A, CA);
-        if (!__any(B.act)) break;
-        A = next(B);
-        issue<TINY>(p, A, j, CA);
-        process(B, CB);
-    }
-    if (p.bad != nullptr && lane == 0) {
-        const uint64_t b = *fcs::wave_bad<kBad>(lds);
-        if (b) atomicAdd(p.bad, (unsigned long long)b);
-    }
+    two_in_flight<Chunk>(
+        first_pos<VAR>(p, (uint64_t)blockIdx.x * (NT / kGroup) + threadIdx.x / kGroup),
+        [&](const Pos &c) { return next_pos<VAR>(p, c, Q); },
+        [&](const Pos &c, Chunk &ch) { issue<TINY>(p, c, j, ch); }, process);
+    flush_bad(fcs::wave_bad<kBad>(lds), lane, p.bad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -211,170 +185,66 @@ __global__ __launch_bounds__(NT, 1) void rxv_kernel(RParams p) {
 // items come from the work dispenser, 16 waves per CU. Quarter g of the wave takes frame g: lane c
 // reads its window [E - e_c - 96, E - e_c) from the slot (e_c = dma_end_off(c); the front lane's
 // leading bytes and the overlap word of lanes 3, 7, 11 masked, so every frame byte is in exactly
-// one lane's words), and its header dwords c and c + 16 from the frame's start in the slot. The
-// CRC is fcs_dma_kernel's (two chains on the 8-replica slice tables, merge, lane shift, row XOR);
-// sums, header decode and verdict are rxv_kernel's, from the same window registers, with the
-// geometry a loop invariant (fixed length). The frame's front lane stores the verdict.
+// one lane's words), and its header dwords c and c + 16 from the frame's start in the slot
+// (frame_walk.hpp's DmaSlots and dma_window). The CRC is fcs_dma_kernel's (two chains on the
+// 8-replica slice tables, merge, lane shift, row XOR); sums, header decode and verdict are
+// rxv_kernel's, from the same window registers, with the geometry a loop invariant (fixed length).
+// The frame's front lane stores the verdict.
 // ---------------------------------------------------------------------------------------------
 template <bool TRAILER>
 __global__ __launch_bounds__(kDmaThreads, 1) void rxv_dma_kernel(RParams p) {
     using namespace fcs;
-    constexpr int kWaves = kDmaThreads / 64;
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kDmaRing + kWaves * kDmaItemBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kDmaRing + (kDmaThreads / 64) * kDmaItemBytes];
     const int tid = threadIdx.x;
-    if (TRAILER) {
-        KParams kp{};
-        kp.blob = p.blob;
-        stage_dma_tables<kDmaThreads>(kp, lds, tid);
-    }
+    if (TRAILER) stage_dma_tables<kDmaThreads>(tables_of(p.blob), lds, tid);
     init_bad<kDmaBad>(lds);
     __syncthreads();
 
     const int lane = tid & 63;
     const int c = lane & (kGroup - 1);     // chunk index back from the frame end
     const int g = lane >> 4;               // frame of the item
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint8_t *slot = lds + kDmaRing + (uint32_t)wave * kDmaItemBytes;
-    const uint32_t h = (uint32_t)(lane >> 3) & 3u, r4 = (uint32_t)(lane & 7) * 4u;
-    const uint32_t B[4] = {r4 + 32u * (0u ^ h), r4 + 32u * (1u ^ h), r4 + 32u * (2u ^ h), r4 + 32u * (3u ^ h)};
-    const uint32_t SEL[4] = {0x0C0C0400u + ((0u ^ h) << 8), 0x0C0C0400u + ((1u ^ h) << 8),
-                             0x0C0C0400u + ((2u ^ h) << 8), 0x0C0C0400u + ((3u ^ h) << 8)};
-    const uint32_t lanebase = kDmaHole + (uint32_t)(lane & 31) * 4u;
+    const DmaSlots G(p, lds, __builtin_amdgcn_readfirstlane(tid >> 6), lane);
 
-    // loop invariants: the window's place in the frame, leading bytes to mask, INV start
-    const uint32_t ec = dma_end_off(c);
-    const int rel = (int)p.flen - (int)ec - kChunkBytes;   // frame position of the window's first byte (>= -28)
+    // loop invariants: the lookups' lane constants, the window's place in the frame, leading bytes
+    // to mask, INV start
+    const DmaLane L = dma_lane((uint32_t)lane);
+    const int rel = (int)p.flen - (int)dma_end_off(c) - kChunkBytes;   // frame position of the window's first byte (>= -28)
     const int zc = (c == kGroup - 1) ? (int)(kDmaCover - p.flen) : (dma_short_lane(c) ? 4 : 0);
-    const uint32_t x0 = (TRAILER && c == kGroup - 1)
-                            ? lds_rd(lds, dma_hole(kDmaInvHole + (uint32_t)zc / 32u) + (uint32_t)(zc % 32) * 4u)
-                            : 0u;
+    const uint32_t x0 = TRAILER ? dma_inv_start(lds, (uint32_t)lane, zc) : 0u;
 
-    const uint64_t lo16 = p.lo4 & ~15ull;
-    const uint64_t smax = ((p.hi4 + 15) & ~15ull) - kDmaItemBytes;   // last slot start inside the arena
-    auto slot_src = [&](uint64_t S) {
-        const uint64_t a = S & ~15ull;
-        return a < lo16 ? lo16 : (a > smax ? smax : a);
-    };
     constexpr uint64_t kEnd = Dispenser::kEnd;
-    Dispenser D(p.ctr, (p.n + 3) >> 2, (uint64_t)gridDim.x * kWaves,
-                (uint64_t)blockIdx.x * kWaves + (uint64_t)wave, lane, 100, 4, 64);
-    auto item_start = [&](uint64_t i) { return p.base + 4 * i * p.stride; };
-    auto dma_of = [&](uint64_t i) {
-        const uint64_t S = item_start(i), sn = slot_src(S);
-        const uint64_t e = S + 3 * p.stride + p.flen + 4 - sn;
-        dma_item(slot, sn, lane, (uint32_t)(e < (uint64_t)kDmaItemBytes ? e : (uint64_t)kDmaItemBytes));
-    };
-
+    Dispenser D = G.dispenser();
     uint64_t it = D.first();
-    if (it != kEnd) dma_of(it);
+    if (it != kEnd) G.dma_of(it);
     while (it != kEnd) {   // wave-uniform
-        const uint64_t f = 4 * it + (uint64_t)g;
-        const uint64_t S = item_start(it), src = slot_src(S);
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's slot DMA has landed
-        // a frame past the batch's end (last item) works on the item's first frame: nothing outside the slot is read
-        const uint64_t goff = f < p.n ? (uint64_t)g * p.stride : 0ull;
-        const int64_t x = (int64_t)(S - src + goff) + rel;   // window start within the slot
-        const uint32_t r = (uint32_t)x & 3u;
-        const uint32_t *wp = reinterpret_cast<const uint32_t *>(slot + (x & ~3ll));
-        uint32_t d[kChunkWords + 1];
-#pragma unroll
-        for (int q = 0; q < kChunkWords; q++) d[q] = wp[q];
-        {   // the 25th dword matters only when r != 0; clamped so the slot is never read past its end
-            const uint64_t a24 = (uint64_t)(wp + kChunkWords), lim = (uint64_t)(slot + kDmaItemBytes - 4);
-            d[kChunkWords] = *reinterpret_cast<const uint32_t *>(a24 < lim ? a24 : lim);
-        }
-        // the frame's first 128 bytes: dwords c and c + 16 from floor4(frame start) in the slot
+        uint32_t d[kChunkWords + 1], r;
         Frame fr;
-        fr.start = S + goff;   // slots start at 16-B pieces: same low address bits
-        fr.len = p.flen;
-        fr.m = 1;
         Chunk ch;
-        {
-            const uint32_t hb = (uint32_t)(S - src + goff) & ~3u;
-            const uint32_t *hp = reinterpret_cast<const uint32_t *>(slot + hb);
-            ch.h0 = hp[c];
-            ch.h1 = hp[c + 16];
-        }
+        const uint64_t f = dma_window(G, it, g, c, rel, d, r, fr, ch);
         __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slot is free for the next DMA
         const uint64_t nxt = D.next(it);
-        if (nxt != kEnd) dma_of(nxt);
+        if (nxt != kEnd) G.dma_of(nxt);
 
         const Hdr H = decode<TRAILER>(fr, ch, c);
         uint32_t w[kChunkWords];
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], r);
-#pragma unroll
-        for (int i = 0; i < kSingleMaskWords; i++) {   // zc <= 28: the first 7 words at most
-            int t = zc - 4 * i;
-            t = t < 0 ? 0 : (t > 4 ? 4 : t);
-            w[i] &= (uint32_t)(0xFFFFFFFFull << (8 * t));
-        }
+        align_words(d, r, w);
+        front_mask(w, zc, 4 * kSingleMaskWords);   // zc <= 28: the first 7 words at most
         uint64_t tot = 0, tail = 0;
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i += 2) tot += (uint64_t)w[i] + w[i + 1];
-        {
-            const int dl = H.cl - rel;
-            const int dt = !H.ps ? kChunkBytes + 4 : (dl < -4 ? -4 : (dl > kChunkBytes + 4 ? kChunkBytes + 4 : dl));
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                if (__any(dt < 24 * (blk + 1))) {
-#pragma unroll
-                    for (int i = 6 * blk; i < 6 * blk + 6; i++) tail += clear_low_bits(w[i], 8 * (dt - 4 * i));
-                }
-            }
-        }
+        add_sums(w, rel, H.cl, H.ps, tot, tail);
         uint32_t v = H.bits;
-        if (TRAILER) {
-            constexpr int CL = kDmaChainWords;
-            uint32_t xs[kDmaChains];
-#pragma unroll
-            for (int hh = 0; hh < kDmaChains; hh++) xs[hh] = w[hh * CL] ^ (hh == 0 ? x0 : 0u);
-#pragma unroll
-            for (int i = 0; i < CL; i++)
-#pragma unroll
-                for (int hh = 0; hh < kDmaChains; hh++)
-                    xs[hh] = step4_l8(lds, xs[hh], i < CL - 1 ? w[hh * CL + i + 1] : 0u, B, SEL);
-            uint32_t mv = xs[kDmaChains - 1];
-#pragma unroll
-            for (int hh = 0; hh < kDmaChains - 1; hh++) mv = merge_shift_dma(lds, kDmaChains - 2 - hh, xs[hh], mv);
-            const uint32_t crc = row_xor(lane_shift_dma(lds, mv, lanebase));
-            if (~crc != kResidue) v |= kFcsBad;
-        }
-        const uint32_t te = fold64(row_sum(fold64(tot))), ta = fold64(row_sum(fold64(tail)));
-        const uint32_t hm = fold64(row_sum(H.sums & 0xffffu)), h0 = fold64(row_sum(H.sums >> 16));
-        const bool oe = p.flen & 1u, om = fr.start & 1ull;
-        const uint32_t tot_s = oe ? swap16(te) : te, tail_s = oe ? swap16(ta) : ta;
-        const uint32_t hdr_s = om ? swap16(hm) : hm, head_s = om ? swap16(h0) : h0;
-        if ((v & (kIpv4 | kIpBadHdr)) == kIpv4 && fold64(0xffffull + hdr_s) != 0xffffu) v |= kIpBadCsum;
-        if (H.ps) {
-            const uint64_t l4 = (uint64_t)H.ps + tot_s + (0xffffu - head_s) + (0xffffu - tail_s);
-            if (fold64(l4) != 0xffffu) v |= kL4BadCsum;
-        }
+        if (TRAILER && ~row_xor(dma_chunk_crc(lds, w, x0, L.B, L.SEL, L.lanebase)) != kResidue) v |= kFcsBad;
+        v = sum_verdict(v, H, tot, tail, p.flen & 1u, fr.start & 1ull);
         const bool st = c == kGroup - 1 && f < p.n;
         if (st) p.verdict[f] = v;
-        const uint64_t mb = __ballot(st && (v & p.bad_mask) != 0u);
-        if (mb != 0 && lane == 0) *wave_bad<kDmaBad>(lds) += (uint64_t)__popcll(mb);
+        count_bad(wave_bad<kDmaBad>(lds), lane, st && (v & p.bad_mask) != 0u);
         it = nxt;
     }
-    if (p.bad != nullptr && lane == 0) {
-        const uint64_t b = *wave_bad<kDmaBad>(lds);
-        if (b) atomicAdd(p.bad, (unsigned long long)b);
-    }
+    flush_bad(wave_bad<kDmaBad>(lds), lane, p.bad);
 }
 
 // The one routing decision (launch_rxv launches what it returns; the engine leases a work counter
 // exactly when it returns kDma).
-Route route(bool var, const RParams &p, uint64_t dma_min) {
-    if (!p.n) return Route::kNone;
-    if (var || p.n <= dma_min) return Route::kGeneral;
-    fcs::KParams k{};
-    k.stride = p.stride;
-    k.flen = p.flen;
-    k.fseg = 1;
-    k.lo4 = p.lo4;
-    k.hi4 = p.hi4;
-    return fcs::fixed_dma(k) ? Route::kDma : Route::kGeneral;
-}
+Route route(bool var, const RParams &p, uint64_t dma_min) { return dma_band_route(var, p, dma_min); }
 
 namespace {
 std::atomic<int> g_last_route{(int)Route::kNone};
@@ -388,25 +258,12 @@ hipError_t launch_rxv(bool var, bool trailer, const RParams &p, int cus, uint64_
     g_last_route.store((int)rt, std::memory_order_relaxed);
     if (rt == Route::kDma) {
         if (!p.ctr) return hipErrorInvalidValue;
-        const uint64_t items = (p.n + 3) / 4, wantd = (items + kDmaThreads / 64 - 1) / (kDmaThreads / 64);
-        const int gd = (int)(wantd < (uint64_t)cus ? wantd : (uint64_t)cus);
+        const int gd = dma_grid(p.n, cus);
         if (trailer) hipLaunchKernelGGL((rxv_dma_kernel<true>), dim3(gd), dim3(kDmaThreads), 0, st, p);
         else hipLaunchKernelGGL((rxv_dma_kernel<false>), dim3(gd), dim3(kDmaThreads), 0, st, p);
         return hipGetLastError();
     }
-    const bool tiny = p.hi4 - p.lo4 < 2 * (uint64_t)kChunkBytes;
-    // one workgroup per CU, persistent over the frames (a quarter-wave per frame)
-    const uint64_t slots = kThreads / kGroup, want = (p.n + slots - 1) / slots;
-    const int grid = (int)(want < (uint64_t)cus ? want : (uint64_t)cus);
-#define RXV_GO(V, T, S) hipLaunchKernelGGL((rxv_kernel<V, T, S, kThreads>), dim3(grid), dim3(kThreads), 0, st, p)
-    if (var) {
-        if (trailer) { if (tiny) RXV_GO(true, true, true); else RXV_GO(true, true, false); }
-        else { if (tiny) RXV_GO(true, false, true); else RXV_GO(true, false, false); }
-    } else {
-        if (trailer) { if (tiny) RXV_GO(false, true, true); else RXV_GO(false, true, false); }
-        else { if (tiny) RXV_GO(false, false, true); else RXV_GO(false, false, false); }
-    }
-#undef RXV_GO
+    FRAME_WALK_LAUNCH(rxv_kernel, var, trailer, walk_tiny(p), walk_grid(p.n, cus), st, p);
     return hipGetLastError();
 }
 

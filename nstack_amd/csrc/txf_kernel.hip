@@ -1,6 +1,6 @@
 // txf_kernel.hip — one-pass TX framing for gfx950: IPv4 datagrams in, wire-ready Ethernet frames
 // out, every payload byte read once and written once (include/nstack_txf.h has the rules and the
-// reference lines they restate). The frame walk is rxv_kernel's (rxv_parts.hpp, fcs_crc.hpp): a
+// reference lines they restate). The frame walk is rxv_kernel's (frame_walk.hpp, fcs_crc.hpp): a
 // QUARTER-WAVE per datagram with an outer loop over its fragments; within a frame lane j owns the
 // 96-byte chunk that ends 96 j bytes before the frame END, longer frames are walked in 1536-byte
 // segments counted from the frame end. A full fragment at mtu 1500 (1506 bytes) is one pass.
@@ -43,7 +43,7 @@
 
 #include "fcs_crc.hpp"
 #include "fcs_tables.hpp"
-#include "rxv_parts.hpp"
+#include "frame_walk.hpp"
 #include "txf_launch.hpp"
 
 namespace txf {
@@ -62,18 +62,6 @@ using rxv::swap16;
 template <typename T>
 __device__ __forceinline__ void gstore(uint64_t addr, T v) {
     *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
-}
-
-// Two independent 12-word chains over a chunk, merged with A_48 (as txs_kernel.hip's).
-__device__ __forceinline__ uint32_t chunk_crc(const uint8_t *lds, const uint32_t (&w)[kChunkWords], uint32_t x0,
-                                              uint32_t tb0, uint32_t tb1) {
-    uint32_t xa = x0 ^ w[0], xb = w[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        xa = fcs::step4(lds, xa, i < 11 ? w[i + 1] : 0u, tb0, tb1);
-        xb = fcs::step4(lds, xb, i < 11 ? w[13 + i] : 0u, tb0, tb1);
-    }
-    return fcs::uniform_shift<fcs::kLdsH48>(lds, xa, xb);
 }
 
 // A datagram that becomes frames (uniform over the row but for the image).
@@ -110,17 +98,13 @@ struct Chunk {
 };
 
 __device__ __forceinline__ int rel_of(const Pos &c, int j) {   // frame position of the chunk's first byte
-    return (int)c.fr.F - kSegBytes * (int)(c.fr.m - 1u - c.k) - kChunkBytes * (j + 1);
+    return (int)rxv::rel_of(c.fr.F, c.fr.m, c.k, j);
 }
 
 template <bool FCSW, int NT>
 __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[FCSW ? fcs::kLdsBytes : 16];
-    if (FCSW) {
-        fcs::KParams kp{};
-        kp.blob = p.blob;
-        fcs::stage_tables<NT>(kp, lds);
-    }
+    if (FCSW) fcs::stage_tables<NT>(rxv::tables_of(p.blob), lds);
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
     uint32_t tb0, tb1;
     fcs::table_bases(lane, tb0, tb1);
@@ -284,18 +268,9 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
         const Frame &fr = c.fr;
         const int rel = rel_of(c, j);
         const bool first = c.k == 0, last = c.act && c.k + 1u == fr.m;
-        uint32_t d[kChunkWords + 1];
-#pragma unroll
-        for (int q = 0; q < 6; q++) {
-            d[4 * q] = ch.x[q].x;
-            d[4 * q + 1] = ch.x[q].y;
-            d[4 * q + 2] = ch.x[q].z;
-            d[4 * q + 3] = ch.x[q].w;
-        }
-        d[kChunkWords] = ch.x6;
-        uint32_t w[kChunkWords];   // word i: frame positions rel + 4 i ..
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], ch.r);
+        uint32_t d[kChunkWords + 1], w[kChunkWords];   // word i: frame positions rel + 4 i ..
+        rxv::unpack(ch.x, ch.x6, d);
+        rxv::align_words(d, ch.r, w);
         // ---- the 14 + hlen bytes in front: from the header image (a first segment shorter than
         //      that leaves the rest of them to the second) ----
         const int hend = 14 + (int)c.g.hlen;
@@ -332,15 +307,8 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
         // ---- CRC over the words as they will be stored ----
         uint32_t crc = 0u;
         if (FCSW) {
-            uint32_t x0 = 0u;
-            if (first) {
-                const int zr = -rel, zi = zr < 0 ? 0 : (zr > kChunkBytes - 1 ? kChunkBytes - 1 : zr);
-                const uint32_t iv = fcs::lds_rd(lds, fcs::kLdsInv + 4u * (uint32_t)zi);
-                x0 = (zr >= 0 && zr < kChunkBytes) ? iv : 0u;
-            }
-            const uint32_t rr = chunk_crc(lds, w, x0, tb0, tb1);
-            s = first ? rr : fcs::uniform_shift<fcs::kLdsJump>(lds, s, rr);
-            if (__any(last)) crc = ~fcs::row_xor(last ? fcs::lane_shift(lds, s, lanebase) : 0u);
+            s = rxv::crc_step(lds, s, w, first, -rel, tb0, tb1);
+            if (__any(last)) crc = ~rxv::crc_join(lds, s, last, lanebase);
         }
         // ---- stores, on the destination's dword grid ----
         const uint64_t da = fr.fo + (uint64_t)(int64_t)rel;
@@ -386,24 +354,13 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
         }
     };
 
-    Pos A, B;
+    Pos A;
     A.jf = A.k = 0;
     A.act = false;
     A.g = Dg{};
     A.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
     advance(A, true);
-    Chunk CA, CB;
-    issue(A, CA);
-    // two items in flight per lane: process one while the other's loads are outstanding
-    while (__any(A.act)) {
-        B = next(A);
-        issue(B, CB);
-        process(A, CA);
-        if (!__any(B.act)) break;
-        A = next(B);
-        issue(A, CA);
-        process(B, CB);
-    }
+    rxv::two_in_flight<Chunk>(A, next, issue, process);
 }
 
 // ---------------------------------------------------------------------------------------------

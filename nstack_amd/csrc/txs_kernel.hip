@@ -1,7 +1,7 @@
 // txs_kernel.hip — one-pass TX sealing for gfx950: the IPv4 header checksum, the TCP / UDP / ICMP
 // checksum and the FCS of every frame of a batch, computed from ONE read of its bytes and stored in
 // place (include/nstack_txs.h has the rules and the reference lines they restate). The mirror image
-// of rxv_kernel.hip, whose frame walk, loads, sums and CRC forms it shares (rxv_parts.hpp,
+// of rxv_kernel.hip, whose frame walk, loads, sums and CRC forms it shares (frame_walk.hpp,
 // fcs_crc.hpp): a QUARTER-WAVE per frame, lane j owns the 96-byte chunk that ends 96 j bytes before
 // the frame end, longer frames are walked in 1536-byte segments counted from the frame END, lane l
 // also holds dwords l and l + 16 of the frame's first 128 bytes.
@@ -39,10 +39,9 @@
 
 #include <atomic>
 
-#include "dispenser.hpp"
 #include "fcs_crc.hpp"
 #include "fcs_tables.hpp"
-#include "rxv_parts.hpp"
+#include "frame_walk.hpp"
 #include "txs_launch.hpp"
 
 namespace txs {
@@ -50,14 +49,11 @@ namespace txs {
 using fcs::kChunkBytes;
 using fcs::kChunkWords;
 using fcs::kGroup;
-using fcs::kSegBytes;
 using rxv::Chunk;
 using rxv::fold64;
 using rxv::Frame;
-using rxv::keep_range;
 using rxv::Pos;
 using rxv::row_get;
-using rxv::row_sum;
 using rxv::RParams;
 using rxv::swap16;
 
@@ -68,8 +64,7 @@ struct THdr {
     uint32_t bits;    // status bits that need no sum
     uint32_t ps;      // L4: accumulator start plus pseudo header; 0 = no L4 sum
     uint32_t old;     // the fields' old content, words of the frame start's grid: IP | L4 << 16
-    uint32_t sums;    // this lane's parts, memory grid, folded: bits 0..15 the IP header's sum, bits 16..31
-                      // the sum of frame bytes [0, 14 + hlen) (both with the old field content)
+    uint32_t sums;    // this lane's rxv::header_sums (both with the old field content)
     int cl;           // frame position of the first byte behind the L4 segment (tail mask)
     int che;          // frame position behind the IP header; 0 = no IP checksum to write
     int ql4;          // frame position of the L4 checksum field; 0 = none to write
@@ -125,12 +120,7 @@ __device__ __forceinline__ THdr decode(const Frame &fr, const Chunk &ch, int j, 
         const uint32_t wd = __builtin_amdgcn_alignbyte(D + 1u < 16u ? b0 : b1, D < 16u ? a0 : a1, r);
         if (h.ql4) h.old |= ((h.ql4 & 2) ? wd >> 16 : wd & 0xffffu) << 16;
     }
-    // this lane's two header dwords: byte 0 of dword D at frame position 4 D - r
-    const int q0 = 4 * j - (int)r, che = h.che;
-    const uint64_t hs = (uint64_t)keep_range(ch.h0, q0, 14, che > 14 ? che : 14) +
-                        keep_range(ch.h1, q0 + 64, 14, che > 14 ? che : 14);
-    const uint64_t h0 = (uint64_t)keep_range(ch.h0, q0, 0, che) + keep_range(ch.h1, q0 + 64, 0, che);
-    h.sums = fold64(hs) | (fold64(h0) << 16);
+    h.sums = rxv::header_sums(ch, j, r, h.che);
     return h;
 }
 
@@ -159,19 +149,18 @@ struct Seal {
 
 __device__ __forceinline__ Seal seal_of(const THdr &H, uint64_t tot, uint64_t tail, bool odd_len, bool odd_start) {
     Seal z{0u, 0u, 0u, 0u};
-    const uint32_t te = fold64(row_sum(fold64(tot))), ta = fold64(row_sum(fold64(tail)));
-    const uint32_t hm = fold64(row_sum(H.sums & 0xffffu)), h0 = fold64(row_sum(H.sums >> 16));
-    // to the frame start's word grid: the end grid differs for an odd length, memory's for an odd start
-    const uint32_t tot_s = odd_len ? swap16(te) : te, tail_s = odd_len ? swap16(ta) : ta;
-    const uint32_t hdr_s = odd_start ? swap16(hm) : hm, head_s = odd_start ? swap16(h0) : h0;
+    const rxv::Sums q = rxv::reduce_sums(tot, tail, H.sums, odd_len, odd_start);
     const uint32_t oip = H.old & 0xffffu, ol4 = H.old >> 16;
     if (H.che) {
-        z.ip = ~fold64(0xffffull + hdr_s + (0xffffu - oip)) & 0xffffu;
+        // three 16-bit terms: summed in 32 bits. Behind rxv::reduce_sums the compiler no longer proves that
+        // itself as it did before, and the 64-bit sum it then forms shows in the variable-length rows
+        // (IMIX without FCS 26.23 and 26.19 against 26.13 and 26.12 ms with this form; before 26.21)
+        z.ip = ~fold64(0xffffu + q.hdr_s + (0xffffu - oip)) & 0xffffu;
         z.dip = z.ip ^ oip;
     }
     if (H.ql4) {
         if (H.ps) {
-            const uint64_t l4 = (uint64_t)H.ps + tot_s + (0xffffu - head_s) + (0xffffu - tail_s) + (0xffffu - ol4);
+            const uint64_t l4 = (uint64_t)H.ps + q.tot_s + (0xffffu - q.head_s) + (0xffffu - q.tail_s) + (0xffffu - ol4);
             z.l4 = ~fold64(l4) & 0xffffu;
             if (z.l4 == 0u && ((H.bits >> kProtoShift) & 0xffu) == 17u) z.l4 = 0xffffu;   // RFC 768
         }
@@ -209,29 +198,13 @@ __device__ __forceinline__ void store_fcs(const TParams &tp, bool st, int j, uin
     if (FCSW && j < 4) reinterpret_cast<uint8_t *>(start)[(uint64_t)F + (uint32_t)j] = (uint8_t)(crc >> (8 * j));
 }
 
-// Two independent 12-word chains over a chunk, merged with A_48 (fcs_kernel.hip).
-__device__ __forceinline__ uint32_t chunk_crc(const uint8_t *lds, const uint32_t (&w)[kChunkWords], uint32_t x0,
-                                              uint32_t tb0, uint32_t tb1) {
-    uint32_t xa = x0 ^ w[0], xb = w[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        xa = fcs::step4(lds, xa, i < 11 ? w[i + 1] : 0u, tb0, tb1);
-        xb = fcs::step4(lds, xb, i < 11 ? w[13 + i] : 0u, tb0, tb1);
-    }
-    return fcs::uniform_shift<fcs::kLdsH48>(lds, xa, xb);
-}
-
 template <bool VAR, bool FCSW, bool TINY, int NT>
 __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
     const RParams &p = tp.r;
     // without the CRC only the per-wave counters live in LDS
     constexpr uint32_t kBad = FCSW ? fcs::kLdsBad : 0u;
     __shared__ __attribute__((aligned(16))) uint8_t lds[FCSW ? fcs::kLdsBytes : 16 * 8];
-    if (FCSW) {
-        fcs::KParams kp{};
-        kp.blob = p.blob;
-        fcs::stage_tables<NT>(kp, lds);
-    }
+    if (FCSW) fcs::stage_tables<NT>(rxv::tables_of(p.blob), lds);
     fcs::init_bad<kBad>(lds);
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
     uint32_t tb0, tb1;
@@ -239,37 +212,14 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
     const uint32_t lanebase = fcs::kLdsLane | ((uint32_t)(lane & 31) * 4u);
     const uint64_t Q = (uint64_t)gridDim.x * (NT / kGroup);   // frame slots in the grid
 
-    auto next = [&](const Pos &c) -> Pos {
-        Pos n = c;
-        n.k = c.k + 1;
-        if (n.k >= c.fr.m) {
-            n.f = c.f + Q;
-            n.k = 0;
-        }
-        n.act = c.act && n.f < p.n;
-        if (n.act && n.k == 0) n.fr = rxv::frame_of<VAR>(p, n.f);
-        return n;
-    };
-
     // per-frame state, carried over the frame's segments
     uint32_t s = 0;            // CRC register
     uint64_t tot = 0, tail = 0;
     THdr H{0u, 0u, 0u, 0u, 0, 0, 0};
 
     auto process = [&](const Pos &c, const Chunk &ch) {
-        uint32_t d[kChunkWords + 1];
-#pragma unroll
-        for (int q = 0; q < 6; q++) {
-            d[4 * q] = ch.x[q].x;
-            d[4 * q + 1] = ch.x[q].y;
-            d[4 * q + 2] = ch.x[q].z;
-            d[4 * q + 3] = ch.x[q].w;
-        }
-        d[kChunkWords] = ch.x6;
-        if (!TINY && __any(ch.dlead)) fcs::shift_up(d, ch.dlead);   // arena start only; uniform
         uint32_t w[kChunkWords];
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], ch.r);
+        rxv::chunk_words<TINY>(ch, w);
         const bool first = c.k == 0;
         if (__any(first)) {   // a frame's first chunk: its header fields
             const THdr hn = decode(c.fr, ch, j, tp.flags);
@@ -279,36 +229,8 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
                 tot = tail = 0;
             }
         }
-        if (first) {   // the front mask
-#pragma unroll
-            for (int i = 0; i < kChunkWords; i++) {
-                if (4 * i < (int)p.zmax) {   // uniform bound: words no front lane can mask are skipped
-                    int t = ch.zr - 4 * i;
-                    t = t < 0 ? 0 : (t > 4 ? 4 : t);
-                    w[i] &= (uint32_t)(0xFFFFFFFFull << (8 * t));
-                }
-            }
-        }
-        // ---- sums (rxv_kernel): every word into the total; words holding bytes from cl on also into the tail ----
-        {
-            uint64_t a = 0;
-#pragma unroll
-            for (int i = 0; i < kChunkWords; i += 2) a += (uint64_t)w[i] + w[i + 1];
-            tot += a;
-            const int64_t rel = (int64_t)c.fr.len - (int64_t)kSegBytes * (int64_t)(c.fr.m - 1 - c.k) -
-                                (int64_t)kChunkBytes * (j + 1);
-            const int64_t dl = (int64_t)H.cl - rel;
-            const int dt = !H.ps ? kChunkBytes + 4 : (dl < -4 ? -4 : (dl > kChunkBytes + 4 ? kChunkBytes + 4 : (int)dl));
-            uint64_t b = 0;
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                if (__any(dt < 24 * (blk + 1))) {
-#pragma unroll
-                    for (int i = 6 * blk; i < 6 * blk + 6; i++) b += fcs::clear_low_bits(w[i], 8 * (dt - 4 * i));
-                }
-            }
-            tail += b;
-        }
+        if (first) rxv::front_mask(w, ch.zr, (int)p.zmax);
+        rxv::add_sums(w, rxv::rel_of(c.fr.len, c.fr.m, c.k, j), H.cl, H.ps, tot, tail);
         // ---- the frame's last chunk: the values; a single-segment frame is patched in its registers ----
         const bool last = c.act && c.k + 1 == c.fr.m;
         Seal z{0u, 0u, 0u, 0u};
@@ -317,22 +239,12 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
             if (FCSW) {
                 const bool one = last && first;
                 // frame position of the chunk's first byte; used for a single segment only (<= 1536 - 96)
-                const int rel = (int)((int64_t)c.fr.len - (int64_t)kChunkBytes * (j + 1));
+                const int rel = (int)rxv::rel_of(c.fr.len, 1u, 0u, j);
                 xor_field(w, one ? 24 - rel : kNoField, z.dip);
                 xor_field(w, one && H.ql4 ? H.ql4 - rel : kNoField, z.dl4);
             }
         }
-        // ---- CRC: two independent 12-word chains, merged with A_48 (fcs_kernel.hip) ----
-        if (FCSW) {
-            uint32_t x0 = 0;
-            if (first) {
-                const int zi = ch.zr < 0 ? 0 : (ch.zr > kChunkBytes - 1 ? kChunkBytes - 1 : ch.zr);
-                const uint32_t iv = fcs::lds_rd(lds, fcs::kLdsInv + 4u * (uint32_t)zi);
-                x0 = (ch.zr >= 0 && ch.zr < kChunkBytes) ? iv : 0u;
-            }
-            const uint32_t rr = chunk_crc(lds, w, x0, tb0, tb1);
-            s = first ? rr : fcs::uniform_shift<fcs::kLdsJump>(lds, s, rr);
-        }
+        if (FCSW) s = rxv::crc_step(lds, s, w, first, ch.zr, tb0, tb1);
         if (__any(last)) {
             uint32_t v = H.bits, crc = 0u;
             if (FCSW) {
@@ -346,13 +258,13 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
                     const bool own_hi = mc && (int)(chi & 15u) == j, own_lo = mc && (int)(clo & 15u) == j;
                     const uint32_t ci = own_hi ? chi : clo;
                     const bool own = own_hi || own_lo;
-                    const int rel = (int)((int64_t)F - (int64_t)kChunkBytes * ((int64_t)ci + 1));
+                    const int rel = (int)rxv::rel_of(F, 1u, 0u, (int)ci);   // chunk ci counted from the frame end
                     uint32_t dw[kChunkWords];
 #pragma unroll
                     for (int i = 0; i < kChunkWords; i++) dw[i] = 0u;
                     xor_field(dw, own ? 24 - rel : kNoField, z.dip);
                     xor_field(dw, own && H.ql4 ? H.ql4 - rel : kNoField, z.dl4);
-                    uint32_t rd = chunk_crc(lds, dw, 0u, tb0, tb1);
+                    uint32_t rd = fcs::chunk_crc(lds, dw, 0u, tb0, tb1);
                     const uint32_t cnt = own ? ci >> 4 : 0u;   // segments behind the chunk's
                     for (uint32_t t = 0; __any(t < cnt); t++) {
                         const uint32_t nx = fcs::uniform_shift<fcs::kLdsJump>(lds, rd, 0u);
@@ -360,18 +272,30 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
                     }
                     s ^= own ? rd : 0u;
                 }
-                uint32_t x = last ? fcs::lane_shift(lds, s, lanebase) : 0u;
-                x = fcs::row_xor(x);
+                const uint32_t x = rxv::crc_join(lds, s, last, lanebase);
                 crc = c.fr.len ? ~x : 0u;
                 v |= kFcsSet;
             }
             store_sums(tp, last, j, c.f, c.fr.start, H, z, v);
             store_fcs<FCSW>(tp, last, j, c.f, c.fr.start, c.fr.len, crc);
-            const uint64_t mb = __ballot(last && j == 15 && (v & p.bad_mask) != 0u);
-            if (mb != 0 && lane == 0) *fcs::wave_bad<kBad>(lds) += (uint64_t)__popcll(mb);
+            rxv::count_bad(fcs::wave_bad<kBad>(lds), lane, last && j == 15 && (v & p.bad_mask) != 0u);
         }
     };
 
+    // rxv::next_pos, first_pos and two_in_flight written out here, the one piece of the walk this
+    // kernel does not share: through them the variable-length rows ran 0.9 % slower than before
+    // (IMIX without FCS 26.43 against 26.19 ms), written out they run as before
+    auto next = [&](const Pos &c) -> Pos {
+        Pos n = c;
+        n.k = c.k + 1;
+        if (n.k >= c.fr.m) {
+            n.f = c.f + Q;
+            n.k = 0;
+        }
+        n.act = c.act && n.f < p.n;
+        if (n.act && n.k == 0) n.fr = rxv::frame_of<VAR>(p, n.f);
+        return n;
+    };
     Pos A, B;
     A.f = (uint64_t)blockIdx.x * (NT / kGroup) + threadIdx.x / kGroup;
     A.k = 0;
@@ -379,7 +303,6 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
     A.fr = A.act ? rxv::frame_of<VAR>(p, A.f) : Frame{0, 0, 1};
     Chunk CA, CB;
     rxv::issue<TINY>(p, A, j, CA);
-    // two items in flight per lane: process one while the other's loads are outstanding
     while (__any(A.act)) {
         B = next(A);
         rxv::issue<TINY>(p, B, j, CB);
@@ -389,10 +312,7 @@ __global__ __launch_bounds__(NT, 1) void txs_kernel(TParams tp) {
         rxv::issue<TINY>(p, A, j, CA);
         process(B, CB);
     }
-    if (p.bad != nullptr && lane == 0) {
-        const uint64_t b = *fcs::wave_bad<kBad>(lds);
-        if (b) atomicAdd(p.bad, (unsigned long long)b);
-    }
+    rxv::flush_bad(fcs::wave_bad<kBad>(lds), lane, p.bad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -408,109 +328,45 @@ template <bool FCSW>
 __global__ __launch_bounds__(kDmaThreads, 1) void txs_dma_kernel(TParams tp) {
     using namespace fcs;
     const RParams &p = tp.r;
-    constexpr int kWaves = kDmaThreads / 64;
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kDmaRing + kWaves * kDmaItemBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kDmaRing + (kDmaThreads / 64) * kDmaItemBytes];
     const int tid = threadIdx.x;
-    if (FCSW) {
-        KParams kp{};
-        kp.blob = p.blob;
-        stage_dma_tables<kDmaThreads>(kp, lds, tid);
-    }
+    if (FCSW) stage_dma_tables<kDmaThreads>(rxv::tables_of(p.blob), lds, tid);
     init_bad<kDmaBad>(lds);
     __syncthreads();
 
     const int lane = tid & 63;
     const int c = lane & (kGroup - 1);     // chunk index back from the frame end
     const int g = lane >> 4;               // frame of the item
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint8_t *slot = lds + kDmaRing + (uint32_t)wave * kDmaItemBytes;
+    const rxv::DmaSlots G(p, lds, __builtin_amdgcn_readfirstlane(tid >> 6), lane);
 
     // loop invariants: the window's place in the frame, leading bytes to mask
-    const uint32_t ec = dma_end_off(c);
-    const int rel = (int)p.flen - (int)ec - kChunkBytes;   // frame position of the window's first byte (>= -28)
+    const int rel = (int)p.flen - (int)dma_end_off(c) - kChunkBytes;   // frame position of the window's first byte (>= -28)
     const int zc = (c == kGroup - 1) ? (int)(kDmaCover - p.flen) : (dma_short_lane(c) ? 4 : 0);
 
-    const uint64_t lo16 = p.lo4 & ~15ull;
-    const uint64_t smax = ((p.hi4 + 15) & ~15ull) - kDmaItemBytes;   // last slot start inside the arena
-    auto slot_src = [&](uint64_t S) {
-        const uint64_t a = S & ~15ull;
-        return a < lo16 ? lo16 : (a > smax ? smax : a);
-    };
     constexpr uint64_t kEnd = Dispenser::kEnd;
-    Dispenser D(p.ctr, (p.n + 3) >> 2, (uint64_t)gridDim.x * kWaves,
-                (uint64_t)blockIdx.x * kWaves + (uint64_t)wave, lane, 100, 4, 64);
-    auto item_start = [&](uint64_t i) { return p.base + 4 * i * p.stride; };
-    auto dma_of = [&](uint64_t i) {
-        const uint64_t S = item_start(i), sn = slot_src(S);
-        const uint64_t e = S + 3 * p.stride + p.flen + 4 - sn;
-        dma_item(slot, sn, lane, (uint32_t)(e < (uint64_t)kDmaItemBytes ? e : (uint64_t)kDmaItemBytes));
-    };
-
+    Dispenser D = G.dispenser();
     uint64_t it = D.first();
-    if (it != kEnd) dma_of(it);
+    if (it != kEnd) G.dma_of(it);
     while (it != kEnd) {   // wave-uniform
-        const uint64_t f = 4 * it + (uint64_t)g;
-        const uint64_t S = item_start(it), src = slot_src(S);
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's slot DMA has landed
-        // a frame past the batch's end (last item) works on the item's first frame: nothing outside the
-        // slot is read, and nothing is stored for it
-        const uint64_t goff = f < p.n ? (uint64_t)g * p.stride : 0ull;
-        const int64_t x = (int64_t)(S - src + goff) + rel;   // window start within the slot
-        const uint32_t r = (uint32_t)x & 3u;
-        const uint32_t *wp = reinterpret_cast<const uint32_t *>(slot + (x & ~3ll));
-        uint32_t d[kChunkWords + 1];
-#pragma unroll
-        for (int q = 0; q < kChunkWords; q++) d[q] = wp[q];
-        {   // the 25th dword matters only when r != 0; clamped so the slot is never read past its end
-            const uint64_t a24 = (uint64_t)(wp + kChunkWords), lim = (uint64_t)(slot + kDmaItemBytes - 4);
-            d[kChunkWords] = *reinterpret_cast<const uint32_t *>(a24 < lim ? a24 : lim);
-        }
-        // the frame's first 128 bytes: dwords c and c + 16 from floor4(frame start) in the slot
+        uint32_t d[kChunkWords + 1], r;
         Frame fr;
-        fr.start = S + goff;   // slots start at 16-B pieces: same low address bits
-        fr.len = p.flen;
-        fr.m = 1;
         Chunk ch;
-        {
-            const uint32_t hb = (uint32_t)(S - src + goff) & ~3u;
-            const uint32_t *hp = reinterpret_cast<const uint32_t *>(slot + hb);
-            ch.h0 = hp[c];
-            ch.h1 = hp[c + 16];
-        }
+        const uint64_t f = rxv::dma_window(G, it, g, c, rel, d, r, fr, ch);   // past the batch's end: nothing is stored
         __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slot is free for the next DMA
         const uint64_t nxt = D.next(it);
-        if (nxt != kEnd) dma_of(nxt);
+        if (nxt != kEnd) G.dma_of(nxt);
 
         const THdr H = decode(fr, ch, c, tp.flags);
         uint32_t w[kChunkWords];
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], r);
-#pragma unroll
-        for (int i = 0; i < kSingleMaskWords; i++) {   // zc <= 28: the first 7 words at most
-            int t = zc - 4 * i;
-            t = t < 0 ? 0 : (t > 4 ? 4 : t);
-            w[i] &= (uint32_t)(0xFFFFFFFFull << (8 * t));
-        }
+        rxv::align_words(d, r, w);
+        rxv::front_mask(w, zc, 4 * kSingleMaskWords);   // zc <= 28: the first 7 words at most
         uint64_t tot = 0, tail = 0;
-#pragma unroll
-        for (int i = 0; i < kChunkWords; i += 2) tot += (uint64_t)w[i] + w[i + 1];
-        {
-            const int dl = H.cl - rel;
-            const int dt = !H.ps ? kChunkBytes + 4 : (dl < -4 ? -4 : (dl > kChunkBytes + 4 ? kChunkBytes + 4 : dl));
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                if (__any(dt < 24 * (blk + 1))) {
-#pragma unroll
-                    for (int i = 6 * blk; i < 6 * blk + 6; i++) tail += clear_low_bits(w[i], 8 * (dt - 4 * i));
-                }
-            }
-        }
+        rxv::add_sums(w, rel, H.cl, H.ps, tot, tail);
         const Seal z = seal_of(H, tot, tail, p.flen & 1u, fr.start & 1ull);
         const bool st = f < p.n;
         const uint32_t v = H.bits | (FCSW ? kFcsSet : 0u);
         store_sums(tp, st, c, f, fr.start, H, z, v);
-        const uint64_t mb = __ballot(st && c == kGroup - 1 && (v & p.bad_mask) != 0u);
-        if (mb != 0 && lane == 0) *wave_bad<kDmaBad>(lds) += (uint64_t)__popcll(mb);
+        rxv::count_bad(wave_bad<kDmaBad>(lds), lane, st && c == kGroup - 1 && (v & p.bad_mask) != 0u);
         uint32_t crc = 0u;
         if (FCSW) {
             // the IP field's place is a loop invariant: kept opaque, or its 48 word compares are
@@ -519,56 +375,26 @@ __global__ __launch_bounds__(kDmaThreads, 1) void txs_dma_kernel(TParams tp) {
             asm volatile("" : "+v"(bip));
             xor_field(w, bip, z.dip);
             xor_field(w, H.ql4 ? H.ql4 - rel : kNoField, z.dl4);
-            // the lookups' per-lane bases and selectors (rxv_dma_kernel's), lane table base and INV start,
-            // formed here from an opaque lane number: as loop invariants they would hold ten registers
-            // through the sums
+            // the lookups' lane constants and the INV start (rxv_dma_kernel's), formed here from an
+            // opaque lane number: as loop invariants they would hold ten registers through the sums
             uint32_t ln = (uint32_t)lane;
             asm volatile("" : "+v"(ln));
-            const uint32_t h = (ln >> 3) & 3u, r4 = (ln & 7u) * 4u;
-            const uint32_t lanebase = kDmaHole + (ln & 31u) * 4u;
-            const uint32_t x0 = (ln & 15u) == (uint32_t)(kGroup - 1)   // the front lane's INV start
-                                    ? lds_rd(lds, dma_hole(kDmaInvHole + (uint32_t)zc / 32u) + (uint32_t)(zc % 32) * 4u)
-                                    : 0u;
-            const uint32_t B[4] = {r4 + 32u * (0u ^ h), r4 + 32u * (1u ^ h), r4 + 32u * (2u ^ h), r4 + 32u * (3u ^ h)};
-            const uint32_t SEL[4] = {0x0C0C0400u + ((0u ^ h) << 8), 0x0C0C0400u + ((1u ^ h) << 8),
-                                     0x0C0C0400u + ((2u ^ h) << 8), 0x0C0C0400u + ((3u ^ h) << 8)};
-            constexpr int CL = kDmaChainWords;
-            uint32_t xs[kDmaChains];
-#pragma unroll
-            for (int hh = 0; hh < kDmaChains; hh++) xs[hh] = w[hh * CL] ^ (hh == 0 ? x0 : 0u);
-#pragma unroll
-            for (int i = 0; i < CL; i++)
-#pragma unroll
-                for (int hh = 0; hh < kDmaChains; hh++)
-                    xs[hh] = step4_l8(lds, xs[hh], i < CL - 1 ? w[hh * CL + i + 1] : 0u, B, SEL);
-            uint32_t mv = xs[kDmaChains - 1];
-#pragma unroll
-            for (int hh = 0; hh < kDmaChains - 1; hh++) mv = merge_shift_dma(lds, kDmaChains - 2 - hh, xs[hh], mv);
-            crc = ~row_xor(lane_shift_dma(lds, mv, lanebase));
+            const uint32_t x0 = dma_inv_start(lds, ln, zc);
+            const DmaLane L = dma_lane(ln);
+            crc = ~row_xor(dma_chunk_crc(lds, w, x0, L.B, L.SEL, L.lanebase));
         }
         store_fcs<FCSW>(tp, st, c, f, fr.start, p.flen, crc);
         it = nxt;
     }
-    if (p.bad != nullptr && lane == 0) {
-        const uint64_t b = *wave_bad<kDmaBad>(lds);
-        if (b) atomicAdd(p.bad, (unsigned long long)b);
-    }
+    rxv::flush_bad(wave_bad<kDmaBad>(lds), lane, p.bad);
 }
 
 // The one routing decision (launch_txs launches what it returns; the engine leases a work counter
 // exactly when it returns kDma).
 Route route(bool var, const TParams &tp, uint64_t dma_min) {
     const RParams &p = tp.r;
-    if (!p.n) return Route::kNone;
-    if (var || p.n <= dma_min) return Route::kGeneral;
-    if ((tp.flags & kFlagFcs) && p.stride < (uint64_t)p.flen + 4) return Route::kGeneral;
-    fcs::KParams k{};
-    k.stride = p.stride;
-    k.flen = p.flen;
-    k.fseg = 1;
-    k.lo4 = p.lo4;
-    k.hi4 = p.hi4;
-    return fcs::fixed_dma(k) ? Route::kDma : Route::kGeneral;
+    if (p.n && (tp.flags & kFlagFcs) && p.stride < (uint64_t)p.flen + 4) return Route::kGeneral;   // no FCS place
+    return rxv::dma_band_route(var, p, dma_min);
 }
 
 namespace {
@@ -585,25 +411,12 @@ hipError_t launch_txs(bool var, const TParams &tp, int cus, uint64_t dma_min, hi
     g_last_route.store((int)rt, std::memory_order_relaxed);
     if (rt == Route::kDma) {
         if (!p.ctr) return hipErrorInvalidValue;
-        const uint64_t items = (p.n + 3) / 4, wantd = (items + kDmaThreads / 64 - 1) / (kDmaThreads / 64);
-        const int gd = (int)(wantd < (uint64_t)cus ? wantd : (uint64_t)cus);
+        const int gd = rxv::dma_grid(p.n, cus);
         if (fcsw) hipLaunchKernelGGL((txs_dma_kernel<true>), dim3(gd), dim3(kDmaThreads), 0, st, tp);
         else hipLaunchKernelGGL((txs_dma_kernel<false>), dim3(gd), dim3(kDmaThreads), 0, st, tp);
         return hipGetLastError();
     }
-    const bool tiny = p.hi4 - p.lo4 < 2 * (uint64_t)kChunkBytes;
-    // one workgroup per CU, persistent over the frames (a quarter-wave per frame)
-    const uint64_t slots = kThreads / kGroup, want = (p.n + slots - 1) / slots;
-    const int grid = (int)(want < (uint64_t)cus ? want : (uint64_t)cus);
-#define TXS_GO(V, T, S) hipLaunchKernelGGL((txs_kernel<V, T, S, kThreads>), dim3(grid), dim3(kThreads), 0, st, tp)
-    if (var) {
-        if (fcsw) { if (tiny) TXS_GO(true, true, true); else TXS_GO(true, true, false); }
-        else { if (tiny) TXS_GO(true, false, true); else TXS_GO(true, false, false); }
-    } else {
-        if (fcsw) { if (tiny) TXS_GO(false, true, true); else TXS_GO(false, true, false); }
-        else { if (tiny) TXS_GO(false, false, true); else TXS_GO(false, false, false); }
-    }
-#undef TXS_GO
+    FRAME_WALK_LAUNCH(txs_kernel, var, fcsw, rxv::walk_tiny(p), rxv::walk_grid(p.n, cus), st, tp);
     return hipGetLastError();
 }
 
