@@ -28,7 +28,11 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "TXS_L4_SHORT", "TXS_PROTO_SHIFT",
            "tx_frame_count", "tx_frame_plan_dev", "tx_frame_dev", "tx_frame_host", "txf_last_launch", "TXF_EXPORTS",
            "TXF_L2_DTYPE", "TXF_F_FCS", "TXF_F_HONOR_DF", "TXF_F_L2_ONE", "TXF_WHOLE", "TXF_FRAGMENTED", "TXF_BAD_HDR",
-           "TXF_BAD_LEN", "TXF_REFRAG", "TXF_DF_DROP", "TXF_NO_ROOM"]
+           "TXF_BAD_LEN", "TXF_REFRAG", "TXF_DF_DROP", "TXF_NO_ROOM",
+           "rx_reasm_plan_host", "rx_reasm_plan_dev", "rx_reasm_dev", "rx_reasm_host", "rxr_last_launch", "rxr_last_host_chunks", "RXR_EXPORTS",
+           "RXR_F_TRAILER", "RXR_WHOLE", "RXR_FRAG", "RXR_HEAD", "RXR_DROPPED", "RXR_NOT_IPV4", "RXR_BAD_HDR",
+           "RXR_BAD_LEN", "RXR_FRAG_BAD", "RXR_INCOMPLETE", "RXR_TOO_BIG", "RXR_NO_ROOM", "RXR_DELIVERED", "RXR_NONE32",
+           "RXR_NONE64"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -78,6 +82,14 @@ TXF_WHOLE, TXF_FRAGMENTED, TXF_BAD_HDR, TXF_BAD_LEN = 0x001, 0x002, 0x004, 0x008
 TXF_REFRAG, TXF_DF_DROP, TXF_NO_ROOM = 0x010, 0x020, 0x040
 # struct txf_l2 as a numpy structured dtype (12 bytes per datagram)
 TXF_L2_DTYPE = [("dst", "u1", (6,)), ("src", "u1", (6,))]
+
+# include/nstack_rxr.h — one-pass RX reassembly (its own list, as RXV_EXPORTS)
+RXR_EXPORTS = ["ether_rx_reasm_plan_host", "ether_rx_reasm_plan_dev", "ether_rx_reasm_dev", "ether_rx_reasm_host",
+               "fcs_debug_rxr_last_launch", "fcs_debug_rxr_last_host_chunks"]
+RXR_F_TRAILER = 1
+RXR_WHOLE, RXR_FRAG, RXR_HEAD, RXR_DROPPED, RXR_NOT_IPV4, RXR_BAD_HDR = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
+RXR_BAD_LEN, RXR_FRAG_BAD, RXR_INCOMPLETE, RXR_TOO_BIG, RXR_NO_ROOM, RXR_DELIVERED = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
+RXR_NONE32, RXR_NONE64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -226,6 +238,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "ether_tx_frame_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
         "ether_tx_frame_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
         "fcs_debug_txf_last_launch": (i32, [c.c_char_p, u64]),
+        "ether_rx_reasm_plan_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "ether_rx_reasm_plan_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ether_rx_reasm_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp]),
+        "ether_rx_reasm_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
+        "fcs_debug_rxr_last_launch": (i32, [c.c_char_p, u64]),
+        "fcs_debug_rxr_last_host_chunks": (c.c_int64, [vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -799,3 +817,60 @@ def txf_last_launch() -> str:
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_txf_last_launch(buf, 32), "fcs_debug_txf_last_launch")
     return buf.value.decode()
+
+
+# ---- one-pass RX reassembly (include/nstack_rxr.h) ----
+def rx_reasm_plan_host(arena, arena_bytes: int, off, length, n: int, fstat, dst, dgi, doff, dlen, dlead=None,
+                       flags: int = 0, verdict=None, drop_mask: int = 0, align: int = 1) -> int:
+    """The plan of a host batch (host arithmetic, no GPU): fstat (u32), dst (u64), dgi (u32) per frame,
+    doff[0..m] (u64), dlen and dlead (u32) per datagram. Returns m; doff[m] is the size of `out`."""
+    return _check(load().ether_rx_reasm_plan_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n,
+                                                  _u32(flags, "flags"), _ptr(verdict), _u32(drop_mask, "drop_mask"),
+                                                  _u32(align, "align"), _ptr(fstat), _ptr(dst), _ptr(dgi), _ptr(doff),
+                                                  _ptr(dlen), _ptr(dlead)),
+                  "ether_rx_reasm_plan_host")
+
+
+def rx_reasm_plan_dev(arena, arena_bytes: int, off, length, n: int, fstat, dst, dgi, doff, dlen, dlead=None, counts=None,
+                      flags: int = 0, verdict=None, drop_mask: int = 0, align: int = 1, stream=None) -> None:
+    """The same arrays in device memory, plus counts[2] = {m, bytes} (u64, optional); asynchronous on `stream`."""
+    _check(load().ether_rx_reasm_plan_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                          _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"), _ptr(fstat),
+                                          _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(dlead), _ptr(counts),
+                                          _stream(stream)),
+           "ether_rx_reasm_plan_dev")
+
+
+def rx_reasm_dev(arena, arena_bytes: int, off, length, n: int, pstat, dst, dgi, doff, dlen, out, out_bytes: int,
+                 flags: int = 0, fstat=None, stream=None) -> None:
+    """Builds the datagrams a plan call placed into `out`; fstat (u32 per frame, optional, may be pstat)
+    gets the final words. Device arrays; asynchronous on `stream`."""
+    _check(load().ether_rx_reasm_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                     _ptr(pstat), _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(out), out_bytes,
+                                     _ptr(fstat), _stream(stream)),
+           "ether_rx_reasm_dev")
+
+
+def rx_reasm_host(arena, arena_bytes: int, off, length, n: int, out, out_bytes: int, flags: int = 0, verdict=None,
+                  drop_mask: int = 0, align: int = 1, fstat=None, doff=None, dlen=None, dlead=None) -> int:
+    """Host form: plans, reassembles a host batch into the host arena `out` and returns the number of
+    datagrams; fstat, doff, dlen and dlead are optional."""
+    return _check(load().ether_rx_reasm_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                             _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"),
+                                             _ptr(out), out_bytes, _ptr(fstat), _ptr(doff), _ptr(dlen), _ptr(dlead)),
+                  "ether_rx_reasm_host")
+
+
+def rxr_last_launch() -> str:
+    """The kernel the last reassembly build launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_rxr_last_launch(buf, 32), "fcs_debug_rxr_last_launch")
+    return buf.value.decode()
+
+
+def rxr_last_host_chunks() -> list:
+    """The datagrams of each chunk the calling thread's last rx_reasm_host cut its batch into."""
+    k = _check(load().fcs_debug_rxr_last_host_chunks(None, 0), "fcs_debug_rxr_last_host_chunks")
+    buf = (ctypes.c_uint64 * max(k, 1))()
+    load().fcs_debug_rxr_last_host_chunks(buf, k)
+    return list(buf[:k])

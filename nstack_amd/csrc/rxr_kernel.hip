@@ -1,0 +1,487 @@
+// rxr_kernel.hip — one-pass RX reassembly for gfx950: received Ethernet frames in, IPv4 datagrams
+// out, every delivered byte read once and written once (include/nstack_rxr.h has the rules and the
+// reference lines they restate).
+//
+// The build kernel. After the plan every frame is independent: it copies one contiguous source range
+// (a whole datagram, a head fragment's header and payload, or another fragment's payload) to
+// out + dst[i]. A QUARTER-WAVE takes a frame; rows take runs of kRun consecutive frames from a zeroed
+// device counter, as txf_kernel's rows take datagrams.
+//   * Two unrelated byte alignments meet. The destination range is cut at the destination's 16-byte
+//     grid: up to 15 bytes in front and up to 15 behind go out as byte stores (one per lane), the
+//     16-byte pieces between them as 16-byte stores, lane j piece j, j + 16, ... with four pieces in
+//     flight. No store touches a byte outside the frame's own destination range (the bytes next to
+//     it belong to another row: the neighbouring fragment or datagram), and no dword is read,
+//     modified and written back.
+//   * A piece's source is 16 bytes at any alignment: the four dwords from floor4(source), a fifth
+//     where the source is not dword-aligned, joined by v_alignbyte. The window of a piece is
+//     [floor4(s), ceil4(s + 16)) with [s, s + 16) inside the frame, so it stays inside
+//     [floor4(frame), ceil4(frame end)) and needs no guard once the frame lies inside the arena
+//     (checked per frame). The range ends are byte loads.
+//   * A head fragment patches ip_len, ip_foff and the checksum in registers on the way: the
+//     checksum comes from a one's-complement sum of its own header dwords with the three fields
+//     masked out (lane j holds header dword j), plus the new ip_len, on the memory grid, as
+//     txf_kernel's header image does it.
+//
+// The plan kernels follow below: classify, insert, link, decide with the block totals, the scan of
+// the totals in one workgroup, place, finish. One frame per thread; no workgroup waits for another;
+// data passes between the phases only across kernel boundaries.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "fcs_crc.hpp"
+#include "ones_fold.hpp"
+#include "rxr_launch.hpp"
+
+namespace rxr {
+
+using fcs::gload;
+using fcs::u32x4a4;
+using ones::fold64;
+using ones::row_sum;
+using ones::swap16;
+
+constexpr int kGroup = 16;     // lanes per frame
+constexpr uint64_t kRun = 8;   // frames a row takes from the work counter at a time
+constexpr int kFlight = 4;     // 16-byte pieces a lane has in flight
+
+template <typename T>
+__device__ __forceinline__ void gstore(uint64_t addr, T v) {
+    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
+}
+
+// Rule 7's three fields: the byte at datagram position pos of a head fragment.
+__device__ __forceinline__ uint32_t patch_byte(uint32_t v, uint32_t pos, uint32_t lenw, uint32_t csum) {
+    if (pos == 2u) return lenw & 0xffu;
+    if (pos == 3u) return lenw >> 8;
+    if (pos == 6u || pos == 7u) return 0u;
+    if (pos == 10u) return csum & 0xffu;
+    if (pos == 11u) return csum >> 8;
+    return v;
+}
+
+__device__ __forceinline__ uint32_t patch_word(uint32_t w, uint32_t p0, uint32_t lenw, uint32_t csum) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const uint32_t nv = patch_byte((w >> (8 * b)) & 0xffu, p0 + (uint32_t)b, lenw, csum);
+        w = (w & ~(0xffu << (8 * b))) | (nv << (8 * b));
+    }
+    return w;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
+    const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
+    const uint32_t T = trailer_of(p.flags);
+    const uint64_t arena_bytes = p.arena_bytes;
+    // this row's run of frames [cur, end), taken from p.ctr
+    uint64_t cur = 0, end = 0;
+    auto take = [&](bool want) {   // wave-uniform call: every row with `want` gets the next run
+        const uint64_t m = __ballot(want && j == 0);
+        if (m == 0) return;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        unsigned long long base = 0;
+        if (lane == leader) base = atomicAdd(p.ctr, (unsigned long long)__popcll(m) * kRun);
+        base = __shfl(base, leader, 64);
+        const uint64_t before = m & ((1ull << (lane & ~(kGroup - 1))) - 1ull);   // wanting rows in front of this one
+        if (want) {
+            cur = base + (uint64_t)__popcll(before) * kRun;
+            end = cur + kRun < p.n ? cur + kRun : p.n;
+        }
+    };
+
+    auto frame = [&](uint64_t i) {
+        const uint32_t st = p.pstat[i];
+        const uint64_t d = p.dst[i];
+        uint32_t fin = st;
+        if (d != kNone64) {
+            const uint32_t k = p.dgi[i], F = p.len[i];
+            const uint64_t fo = p.off[i];
+            // whatever the plan arrays say, nothing outside the frame is read and nothing outside
+            // the datagram's own range inside `out` is written
+            bool ok = (uint64_t)k < p.n && (st & (kWhole | kFrag)) && F >= 34u + T && fo <= arena_bytes && F <= arena_bytes - fo;
+            uint32_t D = 0u, hlen = 0u, I = 0u;
+            uint64_t base = 0;
+            const uint64_t start = p.base + fo;
+            if (ok) {
+                D = p.dlen[k];
+                base = p.doff[k];
+                hlen = ((uint32_t)gload<uint8_t>(start + 14) & 0x0fu) * 4u;
+                I = ((uint32_t)gload<uint8_t>(start + 16) << 8) | (uint32_t)gload<uint8_t>(start + 17);
+                ok = hlen >= 20u && hlen <= I && I <= F - 14u - T;
+            }
+            const bool head = (st & kWhole) || (st & kHead);
+            const uint32_t skip = head ? 0u : hlen, nb = I - skip;
+            ok = ok && has_room(base, D, p.out_bytes) &&                                  // rule 8: the datagram has room
+                 d >= base && d - base <= D && nb <= D - (uint32_t)(d - base);           // and the range lies inside it
+            if (!ok) {
+                fin |= kNoRoom;
+            } else {
+                fin |= kDelivered;
+                const uint64_t s0 = start + 14u + skip, dA = p.out + d;
+                const bool patch = (st & kFrag) && (st & kHead);
+                uint32_t lenw = 0u, csum = 0u;
+                if (patch) {   // rule 7: the header sum without ip_len, ip_foff and the checksum
+                    uint32_t w = 0u;
+                    if ((uint32_t)j < hlen / 4u) {
+                        const uint64_t a = s0 + 4u * (uint32_t)j, a4 = a & ~3ull;
+                        const uint32_t r = (uint32_t)a & 3u;
+                        const uint32_t lo = gload<uint32_t>(a4), hi = r ? gload<uint32_t>(a4 + 4) : 0u;
+                        w = __builtin_amdgcn_alignbyte(hi, lo, r);
+                        if (j < 3) w &= 0x0000ffffu;
+                    }
+                    lenw = swap16(D);
+                    const uint32_t sum = row_sum((w & 0xffffu) + (w >> 16));
+                    csum = ~fold64((uint64_t)sum + lenw) & 0xffffu;
+                }
+                // ---- the bytes in front of the destination's first 16-byte line ----
+                uint32_t nh = (16u - ((uint32_t)dA & 15u)) & 15u;
+                nh = nh < nb ? nh : nb;
+                if ((uint32_t)j < nh) {
+                    uint32_t v = gload<uint8_t>(s0 + (uint32_t)j);
+                    if (patch) v = patch_byte(v, (uint32_t)j, lenw, csum);
+                    gstore<uint8_t>(dA + (uint32_t)j, (uint8_t)v);
+                }
+                // ---- whole 16-byte lines ----
+                const uint32_t nblk = (nb - nh) >> 4;
+                const uint64_t sb = s0 + nh, db = dA + nh;
+                const uint32_t r = (uint32_t)sb & 3u;
+                for (uint32_t b0 = (uint32_t)j; b0 < nblk; b0 += kGroup * kFlight) {
+                    u32x4a4 x[kFlight];
+                    uint32_t x4[kFlight];
+#pragma unroll
+                    for (int q = 0; q < kFlight; q++) {
+                        const uint32_t b = b0 + (uint32_t)(kGroup * q);
+                        x[q] = u32x4a4{0u, 0u, 0u, 0u};
+                        x4[q] = 0u;
+                        if (b < nblk) {
+                            const uint64_t a4 = (sb + 16ull * b) & ~3ull;
+                            x[q] = gload<u32x4a4>(a4);
+                            if (r) x4[q] = gload<uint32_t>(a4 + 16);
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < kFlight; q++) {
+                        const uint32_t b = b0 + (uint32_t)(kGroup * q);
+                        if (b < nblk) {
+                            u32x4a4 y;
+                            y.x = __builtin_amdgcn_alignbyte(x[q].y, x[q].x, r);
+                            y.y = __builtin_amdgcn_alignbyte(x[q].z, x[q].y, r);
+                            y.z = __builtin_amdgcn_alignbyte(x[q].w, x[q].z, r);
+                            y.w = __builtin_amdgcn_alignbyte(x4[q], x[q].w, r);
+                            const uint32_t pos = nh + 16u * b;
+                            if (patch && pos < 12u) {
+                                y.x = patch_word(y.x, pos, lenw, csum);
+                                y.y = patch_word(y.y, pos + 4u, lenw, csum);
+                                y.z = patch_word(y.z, pos + 8u, lenw, csum);
+                                y.w = patch_word(y.w, pos + 12u, lenw, csum);
+                            }
+                            gstore<u32x4a4>(db + 16ull * b, y);
+                        }
+                    }
+                }
+                // ---- the bytes behind the last whole line ----
+                const uint32_t pt = nh + 16u * nblk + (uint32_t)j;
+                if (pt < nb) {
+                    uint32_t v = gload<uint8_t>(s0 + pt);
+                    if (patch) v = patch_byte(v, pt, lenw, csum);
+                    gstore<uint8_t>(dA + pt, (uint8_t)v);
+                }
+            }
+        }
+        if (j == 0 && p.fstat != nullptr) p.fstat[i] = fin;
+    };
+
+    bool done = false;
+    while (true) {
+        take(!done && cur >= end);
+        if (!done && cur >= p.n) done = true;
+        if (__all(done)) break;
+        if (!done) frame(cur++);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan.
+// ---------------------------------------------------------------------------------------------
+// Frame bytes 12..33 of the frame at `start`, from the dwords of its own dword hull inside the arena.
+__device__ __forceinline__ Hdr load_hdr(const RParams &p, uint64_t start, uint32_t F) {
+    const uint64_t a = start + 12, a4 = a & ~3ull, he = (start + F + 3ull) & ~3ull;
+    const uint32_t r = (uint32_t)a & 3u;
+    uint32_t e[7];
+#pragma unroll
+    for (int q = 0; q < 7; q++) {
+        const uint64_t ad = a4 + 4 * q;
+        e[q] = (ad >= p.lo4 && ad + 4 <= he && ad + 4 <= p.hi4) ? gload<uint32_t>(ad) : 0u;
+    }
+    uint32_t w[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) w[q] = __builtin_amdgcn_alignbyte(e[q + 1], e[q], r);
+    Hdr h;
+    h.etype = swap16(w[0] & 0xffffu);
+    h.vhl = (w[0] >> 16) & 0xffu;
+    h.iplen = swap16(w[1] & 0xffffu);
+    h.foff = swap16(w[2] & 0xffffu);
+    h.idp = (w[1] >> 16) | ((w[2] >> 24) << 16);
+    h.src = (w[3] >> 16) | (w[4] << 16);
+    h.dst = (w[4] >> 16) | (w[5] << 16);
+    return h;
+}
+
+__device__ __forceinline__ bool same_key(const Rec &a, uint32_t src, uint32_t dst, uint32_t idp, uint32_t o) {
+    return a.src == src && a.dst == dst && (a.w2 & 0x00ffffffu) == idp && (a.w3 & 0xffffu) == o;
+}
+
+__device__ __forceinline__ uint64_t hash_of(uint32_t src, uint32_t dst, uint32_t idp, uint32_t o) {
+    uint32_t h = src * 0x9E3779B1u ^ dst * 0x85EBCA77u ^ idp * 0xC2B2AE3Du ^ o * 0x27D4EB2Fu;
+    h ^= h >> 15;
+    h *= 0x2C1B3C6Du;
+    h ^= h >> 12;
+    h *= 0x297A2D39u;
+    h ^= h >> 15;
+    return h;
+}
+
+// The entry of (key, o), or tsize when there is none. At most tsize probes; the table holds at most
+// n <= tsize / 2 claims, so an empty entry ends every miss.
+__device__ __forceinline__ uint64_t find(const Scratch &s, uint32_t src, uint32_t dst, uint32_t idp, uint32_t o) {
+    const uint64_t mask = s.tsize - 1;
+    uint64_t h = hash_of(src, dst, idp, o) & mask;
+    for (uint64_t t = 0; t < s.tsize; t++) {
+        const uint32_t c = s.tab[h].claim;
+        if (c == 0u) return s.tsize;
+        if (same_key(s.rec[c - 1u], src, dst, idp, o)) return h;
+        h = (h + 1) & mask;
+    }
+    return s.tsize;
+}
+
+// 1. Rules 1-5 and the key record.
+__global__ __launch_bounds__(kPlanThreads) void rxr_classify_kernel(RParams p, Scratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    if (i >= p.n) return;
+    // a frame that does not lie inside the arena is a frame of no bytes: RXR_NOT_IPV4, nothing of it is read
+    const uint64_t fo = p.off[i];
+    const bool inside = fo <= p.arena_bytes && p.len[i] <= p.arena_bytes - fo;
+    const uint32_t F = inside ? p.len[i] : 0u;
+    const Hdr h = load_hdr(p, p.base + (inside ? fo : 0ull), F);
+    const Cls c = classify(F, p.flags, p.verdict != nullptr && (p.verdict[i] & p.drop_mask) != 0u, h);
+    p.fstat[i] = c.status;
+    Rec rc;
+    rc.src = h.src;
+    rc.dst = h.dst;
+    rc.w2 = (h.idp & 0x00ffffffu) | (c.mf << 24) | ((c.hlen >> 2) << 25) | (groupable(c.status) ? 0x80000000u : 0u);
+    rc.w3 = (c.status & kWhole) ? c.I << 16 : (c.o | (c.L << 16));
+    s.rec[i] = rc;
+    s.headof[i] = kNone32;
+}
+
+// 2. Every fragment claims or joins the entry of its (key, o).
+__global__ __launch_bounds__(kPlanThreads) void rxr_insert_kernel(RParams p, Scratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const Rec me = s.rec[i];
+    if (!(me.w2 & 0x80000000u)) return;
+    const uint32_t idp = me.w2 & 0x00ffffffu, o = me.w3 & 0xffffu;
+    const uint64_t mask = s.tsize - 1;
+    uint64_t h = hash_of(me.src, me.dst, idp, o) & mask;
+    for (uint64_t t = 0; t < s.tsize; t++) {
+        const uint32_t old = atomicCAS(&s.tab[h].claim, 0u, (uint32_t)i + 1u);
+        if (old == 0u || same_key(s.rec[old - 1u], me.src, me.dst, idp, o)) {
+            atomicAdd(&s.tab[h].count, 1u);
+            return;
+        }
+        h = (h + 1) & mask;
+    }
+}
+
+// 3. Every fragment finds its head and its successor and adds itself up on the head's accumulator.
+__global__ __launch_bounds__(kPlanThreads) void rxr_link_kernel(RParams p, Scratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const Rec me = s.rec[i];
+    if (!(me.w2 & 0x80000000u)) return;
+    const uint32_t idp = me.w2 & 0x00ffffffu, o = me.w3 & 0xffffu, L = me.w3 >> 16;
+    const bool mf = (me.w2 >> 24) & 1u;
+    const uint64_t eh = find(s, me.src, me.dst, idp, 0u);
+    if (eh == s.tsize) return;   // no head: headof stays kNone32
+    const uint32_t hc = s.tab[eh].claim - 1u;
+    s.headof[i] = hc;
+    const uint64_t own = o ? find(s, me.src, me.dst, idp, o) : eh;
+    bool fault = own == s.tsize || s.tab[own].count != 1u;              // two fragments with the same o
+    Acc *a = s.acc + hc;
+    if (mf) {
+        fault = fault || find(s, me.src, me.dst, idp, o + L) == s.tsize;   // its end is no fragment's o
+    } else {
+        atomicAdd(&a->lasts, 1u);
+        atomicMax(&a->total, o + L);
+    }
+    atomicAdd(&a->sumL, (unsigned long long)L);
+    if (fault) atomicOr(&a->fault, 1u);
+}
+
+// Inclusive scan over the workgroup; total: the workgroup's sum.
+__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *sh, uint64_t &total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int o = 1; o < kPlanThreads; o <<= 1) {
+        const uint64_t add = t >= o ? sh[t - o] : 0ull;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    const uint64_t r = sh[t];
+    total = sh[kPlanThreads - 1];
+    __syncthreads();   // sh is free for the next call
+    return r;
+}
+
+// 4. Each head decides (rule 6). dgi[i] = 1 on the head frame of a delivered datagram, dst[i] its
+// padded length; the blocks' totals of both.
+__global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scratch s) {
+    __shared__ uint64_t sh[kPlanThreads];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    uint32_t D = 0u, is = 0u;
+    if (i < p.n) {
+        const uint32_t st = p.fstat[i];
+        const Rec me = s.rec[i];
+        if (st & kWhole) {
+            D = me.w3 >> 16;
+            is = 1u;
+        } else if ((st & kHead) && groupable(st) && s.headof[i] == (uint32_t)i) {
+            Acc *a = s.acc + i;
+            const bool complete = a->fault == 0u && a->lasts == 1u && a->sumL == (unsigned long long)a->total;
+            const uint32_t Dd = ((me.w2 >> 25) & 0x0fu) * 4u + a->total;
+            uint32_t state = 0u;
+            if (complete) state = Dd > 65535u ? 2u : 1u;
+            a->state = state;
+            if (state == 1u) {
+                D = Dd;
+                is = 1u;
+            }
+        }
+        if (is) s.acc[i].D = D;
+        p.dgi[i] = is;
+        p.dst[i] = is ? padded(D, p.align) : 0ull;
+    }
+    uint64_t tc, tb;
+    block_scan_incl(is, sh, tc);
+    block_scan_incl(is ? padded(D, p.align) : 0ull, sh, tb);
+    if (threadIdx.x == 0) {
+        s.totc[blockIdx.x] = tc;
+        s.totb[blockIdx.x] = tb;
+    }
+}
+
+// 5. One workgroup: both arrays of block totals become the sums of the blocks in front; counts and
+// doff[m].
+__global__ __launch_bounds__(kPlanThreads) void rxr_scan_totals_kernel(RParams p, Scratch s, uint64_t nb) {
+    __shared__ uint64_t sh[kPlanThreads];
+    uint64_t basec = 0, baseb = 0;
+    for (uint64_t b0 = 0; b0 < nb; b0 += kPlanThreads) {
+        const uint64_t b = b0 + threadIdx.x;
+        const uint64_t vc = b < nb ? s.totc[b] : 0ull, vb = b < nb ? s.totb[b] : 0ull;
+        uint64_t tc, tb;
+        const uint64_t ic = block_scan_incl(vc, sh, tc);
+        const uint64_t ib = block_scan_incl(vb, sh, tb);
+        if (b < nb) {
+            s.totc[b] = basec + ic - vc;
+            s.totb[b] = baseb + ib - vb;
+        }
+        basec += tc;
+        baseb += tb;
+    }
+    if (threadIdx.x == 0) {
+        p.doff[basec] = baseb;
+        if (p.counts != nullptr) {
+            p.counts[0] = basec;
+            p.counts[1] = baseb;
+        }
+    }
+}
+
+// 6. Place (rule 8): the head frame of datagram k writes doff[k], dlen[k], dlead[k] and its own dst
+// and dgi; every other frame gets "none" here.
+__global__ __launch_bounds__(kPlanThreads) void rxr_place_kernel(RParams p, Scratch s) {
+    __shared__ uint64_t sh[kPlanThreads];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    const uint64_t is = i < p.n ? p.dgi[i] : 0ull, pb = i < p.n ? p.dst[i] : 0ull;
+    uint64_t tc, tb;
+    const uint64_t k = s.totc[blockIdx.x] + block_scan_incl(is, sh, tc) - is;
+    const uint64_t at = s.totb[blockIdx.x] + block_scan_incl(pb, sh, tb) - pb;
+    if (i >= p.n) return;
+    if (is) {
+        p.dgi[i] = (uint32_t)k;
+        p.dst[i] = at;
+        p.doff[k] = at;
+        p.dlen[k] = s.acc[i].D;
+        if (p.dlead != nullptr) p.dlead[k] = (uint32_t)i;
+    } else {
+        p.dgi[i] = kNone32;
+        p.dst[i] = kNone64;
+    }
+}
+
+// 7. Finish: every fragment takes its group's fate from its head; the others' place was written by
+// the launch before and is only read here.
+__global__ __launch_bounds__(kPlanThreads) void rxr_finish_kernel(RParams p, Scratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const Rec me = s.rec[i];
+    if (!(me.w2 & 0x80000000u)) return;
+    const uint32_t hc = s.headof[i];
+    const uint32_t state = hc == kNone32 ? 0u : s.acc[hc].state;
+    if (state != 1u) {
+        p.fstat[i] |= state == 2u ? kTooBig : kIncomplete;
+        return;
+    }
+    if (hc == (uint32_t)i) return;   // the head: placed
+    const uint32_t hl = ((s.rec[hc].w2 >> 25) & 0x0fu) * 4u;
+    p.dgi[i] = p.dgi[hc];
+    p.dst[i] = p.dst[hc] + hl + (me.w3 & 0xffffu);
+}
+
+namespace {
+std::atomic<int> g_last_route{(int)Route::kNone};
+}
+Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
+
+hipError_t launch_build(const RParams &p, int cus, hipStream_t st) {
+    (void)hipGetLastError();   // report this launch's own error, not an earlier call's
+    if (!p.n) return hipSuccess;
+    if (!p.ctr) return hipErrorInvalidValue;
+    g_last_route.store((int)Route::kGeneral, std::memory_order_relaxed);
+    // four workgroups per CU at the most, persistent over the frames (a quarter-wave per run of frames)
+    const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
+    const uint64_t most = (uint64_t)cus * 4;
+    const int grid = (int)(want < most ? want : most);
+    hipLaunchKernelGGL((rxr_kernel<kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st) {
+    (void)hipGetLastError();
+    if (!p.n) return hipSuccess;
+    const uint64_t nb = plan_blocks(p.n);
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)nb), t(kPlanThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(rxr_classify_kernel, g, t, 0, st, p, s);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_insert_kernel, g, t, 0, st, p, s);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_link_kernel, g, t, 0, st, p, s);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_decide_kernel, g, t, 0, st, p, s);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_place_kernel, g, t, 0, st, p, s);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rxr_finish_kernel, g, t, 0, st, p, s);
+    return hipGetLastError();
+}
+
+}  // namespace rxr

@@ -1,0 +1,102 @@
+// rxr_launch.hpp — host-side launchers of one-pass RX reassembly (rxr_kernel.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rxr_plan.hpp"
+
+namespace rxr {
+
+// What the kernels read: frame i = [base + off[i], + len[i]); [lo4, hi4) is the readable range of
+// the frame arena, dword-rounded.
+struct RParams {
+    uint64_t base, arena_bytes;
+    uint64_t lo4, hi4;
+    const uint64_t *off;
+    const uint32_t *len;
+    uint64_t n;
+    uint32_t flags, align;
+    // the plan
+    const uint32_t *verdict;   // may be null
+    uint32_t drop_mask;
+    uint32_t *fstat;           // plan: out. build: the final word, may be null
+    uint64_t *dst;
+    uint32_t *dgi;
+    uint64_t *doff;
+    uint32_t *dlen;
+    uint32_t *dlead;           // may be null
+    uint64_t *counts;          // may be null
+    // the build
+    const uint32_t *pstat;
+    uint64_t out, out_bytes;
+    unsigned long long *ctr;   // zeroed device work counter (fcs::launch_with_counter): rows take runs of frames from it
+};
+
+// The plan's scratch (device memory that lives on the stream between the launches).
+struct Rec {   // the key record of a frame, written by the classify launch
+    uint32_t src, dst;
+    uint32_t w2;   // ip_id | ip_proto << 16 | MF << 24 | (hlen / 4) << 25 | groupable << 31
+    uint32_t w3;   // o | L << 16 (RXR_WHOLE: I << 16)
+};
+struct Acc {   // what a group's fragments add up on the record of the frame that claimed (key, 0)
+    unsigned long long sumL;
+    uint32_t total, lasts, fault;
+    uint32_t state;   // 0: not complete, 1: delivered, 2: too big (decide launch)
+    uint32_t D, pad;
+};
+struct Entry {   // open addressing, keyed by (key, o) through the claimant's record
+    uint32_t claim;   // frame index + 1; 0: empty
+    uint32_t count;   // arrivals at this (key, o)
+};
+struct Scratch {
+    Rec *rec;
+    Acc *acc;
+    uint32_t *headof;   // the frame that claimed (key, 0) of a fragment's group, or kNone32
+    Entry *tab;
+    uint64_t tsize;     // a power of two, >= 2 n
+    uint64_t *totc, *totb;   // per-block totals of the two scans
+};
+
+constexpr int kThreads = 512;       // rxr_kernel: 8 waves per CU, a quarter-wave per frame
+constexpr int kPlanThreads = 256;   // the plan kernels: one frame per thread
+
+inline uint64_t table_size(uint64_t n) {
+    uint64_t t = 16;
+    while (t < 2 * n) t <<= 1;
+    return t;
+}
+inline uint64_t plan_blocks(uint64_t n) { return (n + kPlanThreads - 1) / kPlanThreads; }
+// Bytes of scratch, and the carving of one allocation of that size (16-byte aligned parts).
+inline uint64_t scratch_bytes(uint64_t n) {
+    return n * (sizeof(Rec) + sizeof(Acc)) + table_size(n) * sizeof(Entry) + ((n * 4 + 15) & ~15ull) + plan_blocks(n) * 16;
+}
+inline Scratch carve(void *mem, uint64_t n) {
+    Scratch s;
+    uint8_t *p = static_cast<uint8_t *>(mem);
+    s.acc = reinterpret_cast<Acc *>(p);
+    p += n * sizeof(Acc);
+    s.tsize = table_size(n);
+    s.tab = reinterpret_cast<Entry *>(p);
+    p += s.tsize * sizeof(Entry);
+    s.rec = reinterpret_cast<Rec *>(p);
+    p += n * sizeof(Rec);
+    s.headof = reinterpret_cast<uint32_t *>(p);
+    p += (n * 4 + 15) & ~15ull;
+    s.totc = reinterpret_cast<uint64_t *>(p);
+    s.totb = s.totc + plan_blocks(n);
+    return s;
+}
+// The part of the scratch the plan wants zeroed before its first launch: acc and the table (adjacent).
+inline uint64_t zeroed_bytes(uint64_t n) { return n * sizeof(Acc) + table_size(n) * sizeof(Entry); }
+
+enum class Route { kNone, kGeneral };
+Route last_launch();   // what the last launch_build of this process launched (tests)
+
+// The plan of p.n frames: the launches of include/nstack_rxr.h on `st`. `s` is carved scratch whose
+// zeroed part has been zeroed on the stream.
+hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st);
+
+// Copies the delivered frames' bytes on a grid of at most `cus` workgroups; needs p.ctr.
+hipError_t launch_build(const RParams &p, int cus, hipStream_t st);
+
+}  // namespace rxr
