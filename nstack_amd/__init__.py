@@ -32,7 +32,9 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "rx_reasm_plan_host", "rx_reasm_plan_dev", "rx_reasm_dev", "rx_reasm_host", "rxr_last_launch", "rxr_last_host_chunks", "RXR_EXPORTS",
            "RXR_F_TRAILER", "RXR_WHOLE", "RXR_FRAG", "RXR_HEAD", "RXR_DROPPED", "RXR_NOT_IPV4", "RXR_BAD_HDR",
            "RXR_BAD_LEN", "RXR_FRAG_BAD", "RXR_INCOMPLETE", "RXR_TOO_BIG", "RXR_NO_ROOM", "RXR_DELIVERED", "RXR_NONE32",
-           "RXR_NONE64"]
+           "RXR_NONE64",
+           "rx_reasm_l4_dev", "rx_reasm_l4_host", "rxd_last_launch", "RXD_EXPORTS", "RXD_NO_ROOM", "RXD_L4_CHECKED",
+           "RXD_L4_BAD_CSUM", "RXD_L4_SHORT", "RXD_PROTO_SHIFT"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -90,6 +92,11 @@ RXR_F_TRAILER = 1
 RXR_WHOLE, RXR_FRAG, RXR_HEAD, RXR_DROPPED, RXR_NOT_IPV4, RXR_BAD_HDR = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
 RXR_BAD_LEN, RXR_FRAG_BAD, RXR_INCOMPLETE, RXR_TOO_BIG, RXR_NO_ROOM, RXR_DELIVERED = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
 RXR_NONE32, RXR_NONE64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+# include/nstack_rxd.h — reassembly with the L4 verdict of every delivered datagram (its own list, as RXR_EXPORTS)
+RXD_EXPORTS = ["ip_rx_reasm_l4_dev", "ip_rx_reasm_l4_host", "fcs_debug_rxd_last_launch"]
+RXD_NO_ROOM, RXD_L4_CHECKED, RXD_L4_BAD_CSUM, RXD_L4_SHORT = 0x002, 0x080, 0x100, 0x200
+RXD_PROTO_SHIFT = 16
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -244,6 +251,9 @@ def _bind(path: str) -> ctypes.CDLL:
         "ether_rx_reasm_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
         "fcs_debug_rxr_last_launch": (i32, [c.c_char_p, u64]),
         "fcs_debug_rxr_last_host_chunks": (c.c_int64, [vp, u64]),
+        "ip_rx_reasm_l4_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, vp]),
+        "ip_rx_reasm_l4_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, vp, vp]),
+        "fcs_debug_rxd_last_launch": (i32, [c.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -865,6 +875,39 @@ def rxr_last_launch() -> str:
     """The kernel the last reassembly build launch of this process launched."""
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_rxr_last_launch(buf, 32), "fcs_debug_rxr_last_launch")
+    return buf.value.decode()
+
+
+# ---- reassembly with L4 verdicts (include/nstack_rxd.h) ----
+def rx_reasm_l4_dev(arena, arena_bytes: int, off, length, n: int, pstat, dst, dgi, doff, dlen, counts, out, out_bytes: int,
+                    dverdict, flags: int = 0, fstat=None, bad_mask: int = 0, bad=None, stream=None) -> None:
+    """rx_reasm_dev plus dverdict[k] (u32, n entries) = the RXD_* word of delivered datagram k < counts[0];
+    *bad (u64, optional) = datagrams with dverdict & bad_mask. Device arrays; asynchronous on `stream`."""
+    _check(load().ip_rx_reasm_l4_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                     _ptr(pstat), _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(counts), _ptr(out),
+                                     out_bytes, _ptr(fstat), _u32(bad_mask, "bad_mask"), _ptr(dverdict), _ptr(bad),
+                                     _stream(stream)),
+           "ip_rx_reasm_l4_dev")
+
+
+def rx_reasm_l4_host(arena, arena_bytes: int, off, length, n: int, out, out_bytes: int, dverdict, flags: int = 0,
+                     verdict=None, drop_mask: int = 0, align: int = 1, fstat=None, doff=None, dlen=None, dlead=None,
+                     bad_mask: int = 0) -> tuple:
+    """Host form: rx_reasm_host plus dverdict[k] (u32, n entries) for every delivered datagram. Returns
+    (m, the number of datagrams with dverdict & bad_mask)."""
+    bad = ctypes.c_uint64(0)
+    m = _check(load().ip_rx_reasm_l4_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                          _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"), _ptr(out),
+                                          out_bytes, _ptr(fstat), _ptr(doff), _ptr(dlen), _ptr(dlead),
+                                          _u32(bad_mask, "bad_mask"), _ptr(dverdict), ctypes.addressof(bad)),
+               "ip_rx_reasm_l4_host")
+    return m, int(bad.value)
+
+
+def rxd_last_launch() -> str:
+    """The kernel the last reassembly build launch with sums of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_rxd_last_launch(buf, 32), "fcs_debug_rxd_last_launch")
     return buf.value.decode()
 
 

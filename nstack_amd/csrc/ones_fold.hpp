@@ -25,4 +25,31 @@ __device__ __forceinline__ uint32_t row_sum(uint32_t v) {
     return v;
 }
 
+// include/nstack_rxv.h rule 8, stated once for the validator (rxv::decode) and the reassembly verdict
+// (rxd_verdict_kernel): what the check of an L-byte L4 segment of `proto` starts from. src and dst are
+// the header's address words as they lie (little-endian reads), ufield the UDP checksum field.
+//   ps: the accumulator start plus the pseudo header; 0 = no L4 checksum to verify.
+//   tcp_checksum(ntohl(src), ntohl(dst), seg, L): htonl() of both gives back the words as they lie;
+//   udp_checksum(seg, L, src, dst): the raw in_addr_t words; ip_checksum(msg, L) for ICMP.
+// ip_checksum and tcp_checksum start at 0xffff, udp_checksum adds the non-zero protocol word, so the
+// folded total is never 0 and the reference returns 0 exactly when it is 0xffff.
+// A segment too short for its protocol sets `short_bit` (the callers' L4_SHORT) in `bits`.
+__device__ __forceinline__ uint32_t l4_start(uint32_t proto, uint32_t src, uint32_t dst, uint32_t L, uint32_t ufield,
+                                             uint32_t short_bit, uint32_t &bits) {
+    uint32_t ps = 0u;
+    const uint32_t l16 = swap16(L);
+    const uint32_t a4 = (src & 0xffffu) + (src >> 16) + (dst & 0xffffu) + (dst >> 16);
+    if (proto == 6u) {
+        if (L < 20u) bits |= short_bit;
+        else ps = 0xffffu + a4 + 0x0600u + l16;
+    } else if (proto == 17u) {
+        if (L < 8u) bits |= short_bit;
+        else if (ufield != 0u) ps = a4 + 0x1100u + l16;
+    } else if (proto == 1u) {
+        if (L < 4u) bits |= short_bit;
+        else ps = 0xffffu;
+    }
+    return ps;
+}
+
 }  // namespace ones

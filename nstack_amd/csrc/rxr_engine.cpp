@@ -1,4 +1,4 @@
-// rxr_engine.cpp — the C ABI of include/nstack_rxr.h around rxr_kernel.hip.
+// rxr_engine.cpp — the C ABI of include/nstack_rxr.h and include/nstack_rxd.h around rxr_kernel.hip.
 //
 // Device forms validate and launch; the device plan takes its scratch from hipMallocAsync on the
 // caller's stream. The host form plans on the host (rxr_plan.hpp), checks every frame and the
@@ -8,13 +8,16 @@
 // 14 + ip_len bytes: padding and trailer stay behind), the chunk's contiguous output range comes
 // back and its datagrams are copied into the caller's arena one by one. Frames that belong to no
 // delivered datagram never travel. No CPU path: a failure is returned, never answered on the host,
-// and the FCS engine's host-batch and fallback counters are not touched.
+// and the FCS engine's host-batch and fallback counters are not touched. The forms of nstack_rxd.h are
+// the same calls with the summing build and the verdict launch behind it (an L4 request: null for the
+// plain forms); the host form brings a chunk's verdict words back with its datagrams.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
 #include <cstring>
 #include <vector>
 
+#include "../../include/nstack_rxd.h"
 #include "../../include/nstack_rxr.h"
 #include "fcs_device.hpp"
 #include "fcs_error.hpp"
@@ -35,13 +38,21 @@ int check_call(uint32_t flags, uint32_t align, uint64_t n) {
 }
 
 // launch_build with the work counter its rows take their frames from, leased from the FCS engine's
-// ring of device `dev` for this launch.
+// ring of device `dev` for this launch. With p.dverdict (nstack_rxd.h): the accumulators and *bad are
+// zeroed on the stream in front of the build, and the verdict launch follows it.
 int launch(rxr::RParams &p, int dev, int cus, hipStream_t st) {
-    return fcs::launch_with_counter(dev, (void *)st, [&](unsigned long long *ctr) -> int {
+    if (p.dverdict) {
+        HIPTRY(hipMemsetAsync(p.dverdict, 0, p.n * 4, st), "zeroing the datagram accumulators");
+        if (p.bad) HIPTRY(hipMemsetAsync(p.bad, 0, 8, st), "zeroing the bad count");
+    }
+    const int rc = fcs::launch_with_counter(dev, (void *)st, [&](unsigned long long *ctr) -> int {
         p.ctr = ctr;
         HIPTRY(rxr::launch_build(p, cus, st), "launching the rxr kernel");
         return 0;
     });
+    if (rc || !p.dverdict) return rc;
+    HIPTRY(rxr::launch_verdict(p, st), "launching the rxd verdict kernel");
+    return 0;
 }
 
 void set_arena(rxr::RParams &p, const void *arena, uint64_t arena_bytes) {
@@ -63,10 +74,11 @@ static_assert(8190ull * 74 + 65535 <= kInBytes && 65535 + 127 <= kOutBytes && 81
 
 struct RxrPipe;   // names this engine's pipelines (host_pipe.hpp)
 thread_local std::vector<uint64_t> t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
-enum { kIn, kOff, kLen, kStat, kDst, kDgi, kDoff, kDlen, kOut };
+enum { kIn, kOff, kLen, kStat, kDst, kDgi, kDoff, kDlen, kOut, kVerd, kCnt };
 const std::vector<BufSpec> kBufs = {{kInBytes + 64, "rxr staging"}, {kChunkFrames * 8, "off"},  {kChunkFrames * 4, "len"},
                                     {kChunkFrames * 4, "fstat"},    {kChunkFrames * 8, "dst"},  {kChunkFrames * 4, "dgi"},
-                                    {(kChunkDgs + 1) * 8, "doff"},  {kChunkDgs * 4, "dlen"},    {kOutBytes, "rxr datagrams"}};
+                                    {(kChunkDgs + 1) * 8, "doff"},  {kChunkDgs * 4, "dlen"},    {kOutBytes, "rxr datagrams"},
+                                    {kChunkFrames * 4, "dverdict"}, {16, "counts"}};   // nstack_rxd.h: one word per frame of the chunk
 
 // The host plan of the batch and, from it, the frames of every datagram in frame order.
 struct HostPlan {
@@ -75,7 +87,8 @@ struct HostPlan {
     uint64_t m = 0;
 };
 
-int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, uint8_t *out) {
+// dverdict: null for the plain form; else the caller's verdict words (nstack_rxd.h), one per datagram.
+int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, uint8_t *out, uint32_t *dverdict) {
     int dev = 0, cus = 0;
     int rc = fcs::engine_device0(&dev, &cus);
     if (rc) return rc;
@@ -132,8 +145,17 @@ int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, 
         p.dlen = s.d<uint32_t>(kDlen);
         p.out = (uint64_t)s.d<void>(kOut);
         p.out_bytes = ob;
+        if (dverdict) {   // the verdict launch reads the chunk's datagram count from device memory
+            s.h<uint64_t>(kCnt)[0] = nd;
+            s.h<uint64_t>(kCnt)[1] = ob;
+            HIPTRY(hipMemcpyAsync(s.d<void>(kCnt), s.h<void>(kCnt), 16, hipMemcpyHostToDevice, st), "H2D counts");
+            p.counts = s.d<uint64_t>(kCnt);
+            p.dverdict = s.d<uint32_t>(kVerd);
+            p.bad_mask = 0;   // bad is counted on the host
+        }
         if ((rc = launch(p, dev, cus, st))) return rc;
         HIPTRY(hipMemcpyAsync(s.h<void>(kOut), s.d<void>(kOut), ob, hipMemcpyDeviceToHost, st), "D2H datagrams");
+        if (dverdict) HIPTRY(hipMemcpyAsync(s.h<void>(kVerd), s.d<void>(kVerd), nd * 4, hipMemcpyDeviceToHost, st), "D2H verdicts");
         s.i0 = k;   // the chunk's first datagram and their number
         s.n = nd;
         s.live = true;
@@ -143,9 +165,52 @@ int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, 
         const uint64_t base = hp.doff[s.i0];
         for (uint64_t q = s.i0; q < s.i0 + s.n; q++)
             std::memcpy(out + hp.doff[q], s.h<uint8_t>(kOut) + (hp.doff[q] - base), hp.dlen[q]);
+        if (dverdict) std::memcpy(dverdict + s.i0, s.h<uint32_t>(kVerd), s.n * 4);
     };
     rc = run_pipe<RxrPipe>(dev, kDepth, kBufs, m, issue, drain);
     return rc ? (int64_t)rc : (int64_t)m;
+}
+
+// The device build of both headers. l4: the form of nstack_rxd.h, which needs counts and dverdict.
+int build_dev(bool l4, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+              uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi, const uint64_t *doff,
+              const uint32_t *dlen, const uint64_t *counts, void *out, uint64_t out_bytes, uint32_t *fstat,
+              uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad, void *stream) {
+    int rc = check_call(flags, 1u, n);
+    if (rc) return rc;
+    if (n && (!arena || !off || !len || !pstat || !dst || !dgi || !doff || !dlen || (!out && out_bytes)))
+        return fcs::set_error(EINVAL, "null pointer");
+    if (l4 && !counts) return fcs::set_error(EINVAL, "null counts: the verdict launch reads the datagram count there");
+    if (l4 && n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
+    if ((uint64_t)out + out_bytes < (uint64_t)out) return fcs::set_error(EINVAL, "out + out_bytes overflows");
+    int dev = 0, cus = 0;
+    if ((rc = fcs::current_device(&dev, &cus))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (l4 && bad) HIPTRY(hipMemsetAsync(bad, 0, 8, st), "zeroing the bad count");
+        return 0;
+    }
+    rxr::RParams p{};
+    set_arena(p, arena, arena_bytes);
+    p.off = off;
+    p.len = len;
+    p.n = n;
+    p.flags = flags;
+    p.pstat = pstat;
+    p.dst = const_cast<uint64_t *>(dst);
+    p.dgi = const_cast<uint32_t *>(dgi);
+    p.doff = const_cast<uint64_t *>(doff);
+    p.dlen = const_cast<uint32_t *>(dlen);
+    p.out = (uint64_t)out;
+    p.out_bytes = out_bytes;
+    p.fstat = fstat;
+    if (l4) {
+        p.counts = const_cast<uint64_t *>(counts);
+        p.dverdict = dverdict;
+        p.bad = (unsigned long long *)bad;
+        p.bad_mask = bad_mask;
+    }
+    return launch(p, dev, cus, st);
 }
 
 }  // namespace
@@ -216,35 +281,19 @@ int ether_rx_reasm_dev(const void *arena, uint64_t arena_bytes, const uint64_t *
                        uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
                        const uint64_t *doff, const uint32_t *dlen, void *out, uint64_t out_bytes, uint32_t *fstat,
                        void *stream) {
-    int rc = check_call(flags, 1u, n);
-    if (rc) return rc;
-    if (n && (!arena || !off || !len || !pstat || !dst || !dgi || !doff || !dlen || (!out && out_bytes)))
-        return fcs::set_error(EINVAL, "null pointer");
-    if ((uint64_t)out + out_bytes < (uint64_t)out) return fcs::set_error(EINVAL, "out + out_bytes overflows");
-    int dev = 0, cus = 0;
-    if ((rc = fcs::current_device(&dev, &cus))) return rc;
-    if (n == 0) return 0;
-    rxr::RParams p{};
-    set_arena(p, arena, arena_bytes);
-    p.off = off;
-    p.len = len;
-    p.n = n;
-    p.flags = flags;
-    p.pstat = pstat;
-    p.dst = const_cast<uint64_t *>(dst);
-    p.dgi = const_cast<uint32_t *>(dgi);
-    p.doff = const_cast<uint64_t *>(doff);
-    p.dlen = const_cast<uint32_t *>(dlen);
-    p.out = (uint64_t)out;
-    p.out_bytes = out_bytes;
-    p.fstat = fstat;
-    return launch(p, dev, cus, (hipStream_t)stream);
+    return build_dev(false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, nullptr, out, out_bytes, fstat,
+                     0u, nullptr, nullptr, stream);
 }
 
-int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
-                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
-                            void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
-                            uint32_t *dlead) {
+}  // extern "C"
+
+namespace {
+
+// The host form of both headers: dverdict is null for ether_rx_reasm_host.
+int64_t reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                   uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, void *out,
+                   uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen, uint32_t *dlead,
+                   uint32_t *dverdict) {
     t_chunks.clear();
     int rc = check_call(flags, align, n);
     if (rc) return rc;
@@ -291,7 +340,7 @@ int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint6
     int dev = 0, cus = 0;   // no CPU path, also for a batch that delivers nothing
     if ((rc = fcs::engine_device0(&dev, &cus))) return rc;
     int64_t r = (int64_t)hp.m;
-    if (hp.m) r = run_host((const uint8_t *)arena, off, hp, (uint8_t *)out);
+    if (hp.m) r = run_host((const uint8_t *)arena, off, hp, (uint8_t *)out, dverdict);
     if (r < 0) return r;
     for (uint64_t i = 0; i < n && fstat; i++)
         fstat[i] = hp.fstat[i] | (hp.dgi[i] != rxr::kNone32 ? rxr::kDelivered : 0u);
@@ -299,6 +348,45 @@ int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint6
     if (dlen) std::memcpy(dlen, hp.dlen.data(), hp.m * 4);
     if (dlead) std::memcpy(dlead, hp.dlead.data(), hp.m * 4);
     return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
+                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
+                            void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
+                            uint32_t *dlead) {
+    return reasm_host(arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff, dlen,
+                      dlead, nullptr);
+}
+
+// ---- include/nstack_rxd.h ----
+int ip_rx_reasm_l4_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                       uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
+                       const uint64_t *doff, const uint32_t *dlen, const uint64_t *counts, void *out, uint64_t out_bytes,
+                       uint32_t *fstat, uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad, void *stream) {
+    return build_dev(true, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, counts, out, out_bytes, fstat,
+                     bad_mask, dverdict, bad, stream);
+}
+
+int64_t ip_rx_reasm_l4_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
+                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
+                            void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
+                            uint32_t *dlead, uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad) {
+    if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
+    const int64_t m = reasm_host(arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff,
+                                 dlen, dlead, dverdict);
+    if (m < 0 || !bad) return m;
+    *bad = 0;   // counted on the host
+    for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
+    return m;
+}
+
+// The kernel the last build launch with sums of this process launched.
+int fcs_debug_rxd_last_launch(char *out, uint64_t cap) {
+    return copy_name(rxr::last_launch_l4() == rxr::Route::kGeneralL4 ? "general-l4" : "none", out, cap);
 }
 
 // The kernel the last build launch of this process launched.

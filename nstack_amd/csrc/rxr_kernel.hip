@@ -22,6 +22,9 @@
 //     masked out (lane j holds header dword j), plus the new ip_len, on the memory grid, as
 //     txf_kernel's header image does it.
 //
+//   * rxr_kernel<NT, true> is the same copy for include/nstack_rxd.h: it also sums what it stores, per
+//     datagram; rxd_verdict_kernel (behind the plan kernels) turns the sums into L4 verdicts.
+//
 // The plan kernels follow below: classify, insert, link, decide with the block totals, the scan of
 // the totals in one workgroup, place, finish. One frame per thread; no workgroup waits for another;
 // data passes between the phases only across kernel boundaries.
@@ -70,7 +73,13 @@ __device__ __forceinline__ uint32_t patch_word(uint32_t w, uint32_t p0, uint32_t
     return w;
 }
 
-template <int NT>
+// A byte stored at address a, on the destination memory's 16-bit grid.
+__device__ __forceinline__ uint32_t grid_byte(uint64_t a, uint32_t v) { return (a & 1ull) ? v << 8 : v; }
+
+// SUM: the build of include/nstack_rxd.h. Every byte a frame stores is also added to a per-lane
+// one's-complement sum on the destination memory's 16-bit grid (the patched header fields as stored);
+// the row's folded sum goes to the datagram's accumulator p.dverdict[k] with one atomic add per frame.
+template <int NT, bool SUM>
 __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
     const uint32_t T = trailer_of(p.flags);
@@ -122,6 +131,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                 const uint64_t s0 = start + 14u + skip, dA = p.out + d;
                 const bool patch = (st & kFrag) && (st & kHead);
                 uint32_t lenw = 0u, csum = 0u;
+                uint32_t acc = 0u;   // SUM: at most 256 lines of eight halves and two bytes per lane, below 2^28
                 if (patch) {   // rule 7: the header sum without ip_len, ip_foff and the checksum
                     uint32_t w = 0u;
                     if ((uint32_t)j < hlen / 4u) {
@@ -142,6 +152,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                     uint32_t v = gload<uint8_t>(s0 + (uint32_t)j);
                     if (patch) v = patch_byte(v, (uint32_t)j, lenw, csum);
                     gstore<uint8_t>(dA + (uint32_t)j, (uint8_t)v);
+                    if (SUM) acc += grid_byte(dA + (uint32_t)j, v);
                 }
                 // ---- whole 16-byte lines ----
                 const uint32_t nblk = (nb - nh) >> 4;
@@ -178,6 +189,9 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                                 y.w = patch_word(y.w, pos + 12u, lenw, csum);
                             }
                             gstore<u32x4a4>(db + 16ull * b, y);
+                            if (SUM)   // db is 16-byte aligned: eight halves of the memory grid
+                                acc += (y.x & 0xffffu) + (y.x >> 16) + (y.y & 0xffffu) + (y.y >> 16) + (y.z & 0xffffu) +
+                                       (y.z >> 16) + (y.w & 0xffffu) + (y.w >> 16);
                         }
                     }
                 }
@@ -187,6 +201,15 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                     uint32_t v = gload<uint8_t>(s0 + pt);
                     if (patch) v = patch_byte(v, pt, lenw, csum);
                     gstore<uint8_t>(dA + pt, (uint8_t)v);
+                    if (SUM) acc += grid_byte(dA + pt, v);
+                }
+                if (SUM) {
+                    // a frame stores at most 65535 bytes, so the row's sum stays below 2^31
+                    const uint32_t part = fold64(row_sum(acc));
+                    // No overflow of the u32 accumulator: a delivered datagram has at most 8192 frames
+                    // (distinct fragment offsets, multiples of 8 below 65536) of at most 0xffff each, and
+                    // starts at 0: the total stays below 2^29. Integer adds commute: no order dependence.
+                    if (j == 0 && part) atomicAdd(p.dverdict + k, part);
                 }
             }
         }
@@ -443,21 +466,105 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_finish_kernel(RParams p, Scr
     p.dst[i] = p.dst[hc] + hl + (me.w3 & 0xffffu);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The datagram verdicts (include/nstack_rxd.h). One thread per datagram k < counts[0], launched over
+// n threads behind the summing build: dverdict[k] holds the sum of everything the build stored of
+// datagram k, on the memory grid. The delivered header is read back from `out` and its sum
+// subtracted; what is left is the L4 segment's sum on the memory grid, byte-swapped when the
+// segment starts at an odd address (P = swap16(fold(M)), inet_kernel.hip); the pseudo header is
+// ones::l4_start's, as in rxv::decode.
+// ---------------------------------------------------------------------------------------------
+// One's-complement sum of the bytes [a, a + nb) on the memory's 16-bit grid: bytes up to the first
+// dword boundary, whole dwords, the bytes behind the last one. Nothing outside the range is read.
+__device__ __forceinline__ uint32_t grid_sum(uint64_t a, uint32_t nb) {
+    uint32_t s = 0u, q = 0u;
+    for (; q < nb && ((a + q) & 3ull); q++) s += grid_byte(a + q, gload<uint8_t>(a + q));
+    for (; q + 4u <= nb; q += 4u) {
+        const uint32_t w = gload<uint32_t>(a + q);
+        s += (w & 0xffffu) + (w >> 16);
+    }
+    for (; q < nb; q++) s += grid_byte(a + q, gload<uint8_t>(a + q));
+    return s;
+}
+
+__device__ __forceinline__ uint32_t load_le32(uint64_t a) {   // any alignment
+    return (uint32_t)gload<uint8_t>(a) | ((uint32_t)gload<uint8_t>(a + 1) << 8) | ((uint32_t)gload<uint8_t>(a + 2) << 16) |
+           ((uint32_t)gload<uint8_t>(a + 3) << 24);
+}
+
+__global__ __launch_bounds__(kPlanThreads) void rxd_verdict_kernel(RParams p) {
+    __shared__ unsigned int wg_bad;
+    if (threadIdx.x == 0) wg_bad = 0u;
+    __syncthreads();
+    const uint64_t k = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    const uint64_t m = p.counts[0] < p.n ? p.counts[0] : p.n;
+    bool is_bad = false;
+    if (k < m) {
+        const uint32_t D = p.dlen[k];
+        const uint64_t at = p.doff[k];
+        uint32_t v = 0u;
+        if (!has_room(at, D, p.out_bytes)) {
+            v = kDgNoRoom;                                    // rule 8 of nstack_rxr.h: nothing was written
+        } else if (D >= 20u) {                                // (a plan call's datagram always has its header)
+            const uint64_t a = p.out + at;
+            const uint32_t hlen = ((uint32_t)gload<uint8_t>(a) & 0x0fu) * 4u;
+            if (hlen >= 20u && hlen <= D) {
+                const uint32_t proto = gload<uint8_t>(a + 9), L = D - hlen;
+                v = proto << kDgProtoShift;
+                const uint32_t ufield = (proto == 17u && L >= 8u)
+                                            ? (uint32_t)gload<uint8_t>(a + hlen + 6) | ((uint32_t)gload<uint8_t>(a + hlen + 7) << 8)
+                                            : 0u;
+                const uint32_t ps = ones::l4_start(proto, load_le32(a + 12), load_le32(a + 16), L, ufield, kDgL4Short, v);
+                if (ps) {
+                    // everything stored minus the header, on the memory grid; then on the segment's own
+                    const uint32_t mem = fold64((uint64_t)fold64(p.dverdict[k]) + (0xffffu - fold64(grid_sum(a, hlen))));
+                    const uint32_t seg = ((a + hlen) & 1ull) ? swap16(mem) : mem;
+                    v |= kDgL4Checked;
+                    if (fold64((uint64_t)ps + seg) != 0xffffu) v |= kDgL4BadCsum;
+                }
+            }
+        }
+        p.dverdict[k] = v;
+        is_bad = (v & p.bad_mask) != 0u;
+    }
+    // bad: counted per wave, added once per workgroup
+    const uint64_t mb = __ballot(is_bad);
+    if (mb != 0 && (threadIdx.x & 63) == 0) atomicAdd(&wg_bad, (unsigned int)__popcll(mb));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_bad != 0u && p.bad != nullptr) atomicAdd(p.bad, (unsigned long long)wg_bad);
+}
+
 namespace {
-std::atomic<int> g_last_route{(int)Route::kNone};
+std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone};
 }
 Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
+Route last_launch_l4() { return (Route)g_last_route_l4.load(std::memory_order_relaxed); }
 
 hipError_t launch_build(const RParams &p, int cus, hipStream_t st) {
     (void)hipGetLastError();   // report this launch's own error, not an earlier call's
     if (!p.n) return hipSuccess;
     if (!p.ctr) return hipErrorInvalidValue;
-    g_last_route.store((int)Route::kGeneral, std::memory_order_relaxed);
     // four workgroups per CU at the most, persistent over the frames (a quarter-wave per run of frames)
     const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
     const uint64_t most = (uint64_t)cus * 4;
     const int grid = (int)(want < most ? want : most);
-    hipLaunchKernelGGL((rxr_kernel<kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    if (p.dverdict) {
+        g_last_route_l4.store((int)Route::kGeneralL4, std::memory_order_relaxed);
+        hipLaunchKernelGGL((rxr_kernel<kThreads, true>), dim3(grid), dim3(kThreads), 0, st, p);
+    } else {
+        g_last_route.store((int)Route::kGeneral, std::memory_order_relaxed);
+        hipLaunchKernelGGL((rxr_kernel<kThreads, false>), dim3(grid), dim3(kThreads), 0, st, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_verdict(const RParams &p, hipStream_t st) {
+    (void)hipGetLastError();
+    if (!p.n) return hipSuccess;
+    if (!p.dverdict || !p.counts) return hipErrorInvalidValue;
+    const uint64_t nb = plan_blocks(p.n);
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rxd_verdict_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p);
     return hipGetLastError();
 }
 

@@ -30,6 +30,10 @@ struct RParams {
     const uint32_t *pstat;
     uint64_t out, out_bytes;
     unsigned long long *ctr;   // zeroed device work counter (fcs::launch_with_counter): rows take runs of frames from it
+    // the build with L4 sums and the verdict launch (include/nstack_rxd.h); all null / 0 for the plain build
+    uint32_t *dverdict;        // n words: the build's per-datagram accumulators, then the verdicts
+    unsigned long long *bad;   // may be null
+    uint32_t bad_mask;
 };
 
 // The plan's scratch (device memory that lives on the stream between the launches).
@@ -89,14 +93,21 @@ inline Scratch carve(void *mem, uint64_t n) {
 // The part of the scratch the plan wants zeroed before its first launch: acc and the table (adjacent).
 inline uint64_t zeroed_bytes(uint64_t n) { return n * sizeof(Acc) + table_size(n) * sizeof(Entry); }
 
-enum class Route { kNone, kGeneral };
-Route last_launch();   // what the last launch_build of this process launched (tests)
+enum class Route { kNone, kGeneral, kGeneralL4 };
+Route last_launch();      // what the last plain launch_build of this process launched (tests)
+Route last_launch_l4();   // what the last launch_build with p.dverdict launched (tests)
 
 // The plan of p.n frames: the launches of include/nstack_rxr.h on `st`. `s` is carved scratch whose
 // zeroed part has been zeroed on the stream.
 hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st);
 
-// Copies the delivered frames' bytes on a grid of at most `cus` workgroups; needs p.ctr.
+// Copies the delivered frames' bytes on a grid of at most `cus` workgroups; needs p.ctr. With
+// p.dverdict (zeroed on the stream) the summing instantiation runs: every frame also adds the
+// one's-complement sum of the bytes it stores to dverdict[dgi[i]].
 hipError_t launch_build(const RParams &p, int cus, hipStream_t st);
+
+// The verdict word of every datagram k < min(counts[0], n) from dverdict[k] as launch_build left it
+// and the delivered header in `out`; *bad (zeroed on the stream) counts verdict & bad_mask.
+hipError_t launch_verdict(const RParams &p, hipStream_t st);
 
 }  // namespace rxr

@@ -21,6 +21,8 @@ namespace rxr {
 constexpr uint32_t kWhole = 0x001u, kFrag = 0x002u, kHead = 0x004u, kDropped = 0x008u, kNotIpv4 = 0x010u,
                    kBadHdr = 0x020u, kBadLen = 0x040u, kFragBad = 0x080u, kIncomplete = 0x100u, kTooBig = 0x200u,
                    kNoRoom = 0x400u, kDelivered = 0x800u;
+// Datagram verdict bits (include/nstack_rxd.h; the L4 bits have nstack_rxv.h's values).
+constexpr uint32_t kDgNoRoom = 0x002u, kDgL4Checked = 0x080u, kDgL4BadCsum = 0x100u, kDgL4Short = 0x200u, kDgProtoShift = 16u;
 constexpr uint32_t kFlagTrailer = 1u, kKnownFlags = 1u;
 constexpr uint32_t kNone32 = 0xffffffffu;
 constexpr uint64_t kNone64 = ~0ull;

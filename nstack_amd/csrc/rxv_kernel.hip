@@ -83,18 +83,7 @@ __device__ __forceinline__ Hdr decode(const Frame &fr, const Chunk &ch, int j) {
             if (foff & 0x3fffu) {
                 h.bits |= kFrag;
             } else if (hlen <= iplen && iplen <= P) {
-                const uint32_t L = iplen - hlen, l16 = swap16(L);
-                const uint32_t a4 = (src & 0xffffu) + (src >> 16) + (dst & 0xffffu) + (dst >> 16);
-                if (proto == 6u) {          // tcp_checksum(ntohl(src), ntohl(dst), seg, L): htonl() of both
-                    if (L < 20u) h.bits |= kL4Short;   // gives back the words as they lie in the header
-                    else h.ps = 0xffffu + a4 + 0x0600u + l16;
-                } else if (proto == 17u) {  // udp_checksum(seg, L, src, dst): the raw in_addr_t words
-                    if (L < 8u) h.bits |= kL4Short;
-                    else if (ufield != 0u) h.ps = a4 + 0x1100u + l16;
-                } else if (proto == 1u) {   // ip_checksum(msg, L)
-                    if (L < 4u) h.bits |= kL4Short;
-                    else h.ps = 0xffffu;
-                }
+                h.ps = ones::l4_start(proto, src, dst, iplen - hlen, ufield, kL4Short, h.bits);   // rule 8
                 if (h.ps) {
                     h.bits |= kL4Checked;
                     h.cl = 14 + (int)iplen;
