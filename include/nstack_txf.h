@@ -55,6 +55,8 @@
  *  10. L4 checksums are NOT touched. A fragmented datagram's UDP or TCP checksum spans its fragments
  *      and must be in place before framing: use inet_csum_* (nstack_inet.h), or leave 0 for UDP as
  *      src/udp.c:192 effectively does. TXF_WHOLE frames can go through ether_tx_seal_* afterwards.
+ *      ip_tx_frame_l4_* (nstack_txd.h) is this build with the L4 checksum of every datagram filled
+ *      in the same launch: it removes that extra pass.
  * A produced frame (F + 4 bytes with TXF_F_FCS) passes ether_rx_validate_* with RXV_F_TRAILER with
  * no defect bit other than RXV_FRAG on fragments and RXV_IP_BAD_LEN on padded frames (I < 56).
  *

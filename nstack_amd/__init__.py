@@ -34,7 +34,9 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "RXR_BAD_LEN", "RXR_FRAG_BAD", "RXR_INCOMPLETE", "RXR_TOO_BIG", "RXR_NO_ROOM", "RXR_DELIVERED", "RXR_NONE32",
            "RXR_NONE64",
            "rx_reasm_l4_dev", "rx_reasm_l4_host", "rxd_last_launch", "RXD_EXPORTS", "RXD_NO_ROOM", "RXD_L4_CHECKED",
-           "RXD_L4_BAD_CSUM", "RXD_L4_SHORT", "RXD_PROTO_SHIFT"]
+           "RXD_L4_BAD_CSUM", "RXD_L4_SHORT", "RXD_PROTO_SHIFT",
+           "tx_frame_l4_dev", "tx_frame_l4_host", "txd_last_launch", "TXD_EXPORTS", "TXD_F_UDP_ZERO", "TXD_L4_CSUM_SET",
+           "TXD_L4_SHORT", "TXD_PROTO_SHIFT"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -97,6 +99,12 @@ RXR_NONE32, RXR_NONE64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 RXD_EXPORTS = ["ip_rx_reasm_l4_dev", "ip_rx_reasm_l4_host", "fcs_debug_rxd_last_launch"]
 RXD_NO_ROOM, RXD_L4_CHECKED, RXD_L4_BAD_CSUM, RXD_L4_SHORT = 0x002, 0x080, 0x100, 0x200
 RXD_PROTO_SHIFT = 16
+
+# include/nstack_txd.h — TX framing with the L4 checksum of every datagram (its own list, as RXD_EXPORTS)
+TXD_EXPORTS = ["ip_tx_frame_l4_dev", "ip_tx_frame_l4_host", "fcs_debug_txd_last_launch"]
+TXD_F_UDP_ZERO = 0x100
+TXD_L4_CSUM_SET, TXD_L4_SHORT = 0x080, 0x200
+TXD_PROTO_SHIFT = 16
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -245,6 +253,9 @@ def _bind(path: str) -> ctypes.CDLL:
         "ether_tx_frame_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
         "ether_tx_frame_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
         "fcs_debug_txf_last_launch": (i32, [c.c_char_p, u64]),
+        "ip_tx_frame_l4_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
+        "ip_tx_frame_l4_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
+        "fcs_debug_txd_last_launch": (i32, [c.c_char_p, u64]),
         "ether_rx_reasm_plan_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "ether_rx_reasm_plan_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ether_rx_reasm_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp]),
@@ -826,6 +837,33 @@ def txf_last_launch() -> str:
     """The kernel the last frame-building launch of this process launched."""
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_txf_last_launch(buf, 32), "fcs_debug_txf_last_launch")
+    return buf.value.decode()
+
+
+# ---- TX framing with L4 checksums (include/nstack_txd.h) ----
+def tx_frame_l4_dev(dgram, dgram_bytes: int, off, length, l2, n: int, mtu: int, first, out, slot: int, slots: int,
+                    flags: int = TXF_F_FCS, flen=None, status=None, fcs=None, stream=None) -> None:
+    """tx_frame_dev plus the TCP / UDP / ICMP checksum of every datagram, stored in the frame that carries
+    the field; status[i] also holds the TXD_* bits. Device arrays; asynchronous on `stream`."""
+    _check(load().ip_tx_frame_l4_dev(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), n, _u32(mtu, "mtu"),
+                                     _u32(flags, "flags"), _ptr(first), _ptr(out), slot, slots, _ptr(flen),
+                                     _ptr(status), _ptr(fcs), _stream(stream)),
+           "ip_tx_frame_l4_dev")
+
+
+def tx_frame_l4_host(dgram, dgram_bytes: int, off, length, l2, n: int, mtu: int, out, slot: int, slots: int,
+                     flags: int = TXF_F_FCS, flen=None, status=None) -> int:
+    """Host form: tx_frame_host plus the L4 checksum of every datagram. Returns the number of frames."""
+    return _check(load().ip_tx_frame_l4_host(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), n,
+                                             _u32(mtu, "mtu"), _u32(flags, "flags"), _ptr(out), slot, slots,
+                                             _ptr(flen), _ptr(status)),
+                  "ip_tx_frame_l4_host")
+
+
+def txd_last_launch() -> str:
+    """The kernel the last launch of tx_frame_l4_dev / tx_frame_l4_host of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_txd_last_launch(buf, 32), "fcs_debug_txd_last_launch")
     return buf.value.decode()
 
 

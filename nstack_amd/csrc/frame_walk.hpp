@@ -1,8 +1,8 @@
 // frame_walk.hpp — the quarter-wave frame walk, written once for rxv_kernel.hip, txs_kernel.hip and
 // txf_kernel.hip: the frame and chunk geometry (Frame, Pos, Geo, Chunk, issue, next_pos), a chunk's
 // words (chunk_words), the front mask, the total and tail sums and their reduction to the frame
-// start's word grid, the header-field extraction, the per-wave count and the two-items-in-flight
-// driver; and for the LDS-DMA pair (rxv_dma_kernel, txs_dma_kernel) the slot geometry and the
+// start's word grid, the header-field extraction, the in-register patch of a 16-bit field
+// (xor_field), the per-wave count and the two-items-in-flight driver; and for the LDS-DMA pair (rxv_dma_kernel, txs_dma_kernel) the slot geometry and the
 // window read. The rules of the walk live here; the kernels add what is their own (verdict; patch
 // and stores; header image, padding and stores). One rule is stated twice on purpose: geo_of forms
 // the chunk address from the frame's end and not through rel_of, which cost three 64-bit adds per
@@ -275,6 +275,26 @@ __device__ __forceinline__ Sums reduce_sums(uint64_t tot, uint64_t tail, uint32_
     const uint32_t hm = fold64(row_sum(hsums & 0xffffu)), h0 = fold64(row_sum(hsums >> 16));
     return Sums{odd_len ? swap16(te) : te, odd_len ? swap16(ta) : ta, odd_start ? swap16(hm) : hm,
                 odd_start ? swap16(h0) : h0};
+}
+
+// ---- a 16-bit field in a chunk's words (the TX kernels patch checksum fields in registers) ----
+constexpr int kNoField = 1 << 20;   // a chunk byte offset no chunk has
+
+// XORs the 16-bit value `delta` (its low byte first) into the chunk words at chunk byte offset b,
+// by bytes: b = -1 reaches only the second byte (word 0), b = 95 only the first; any other b outside
+// [0, 95) does nothing. Only the 6-word blocks some lane of the wave has such bytes in are touched.
+__device__ __forceinline__ void xor_field(uint32_t (&w)[kChunkWords], int b, uint32_t delta) {
+    const bool in = b >= -1 && b < kChunkBytes;
+    const int iw = b >> 2;   // -1 for b = -1
+    const uint64_t P = (uint64_t)delta << (8 * (b & 3));
+    const uint32_t P0 = in ? (uint32_t)P : 0u, P1 = in ? (uint32_t)(P >> 32) : 0u;
+#pragma unroll
+    for (int blk = 0; blk < 4; blk++) {
+        if (__any(in && iw + 1 >= 6 * blk && iw < 6 * blk + 6)) {
+#pragma unroll
+            for (int i = 6 * blk; i < 6 * blk + 6; i++) w[i] ^= (i == iw ? P0 : 0u) ^ (i == iw + 1 ? P1 : 0u);
+        }
+    }
 }
 
 // ---- the per-wave count (wb = fcs::wave_bad of the kernel's LDS) ----

@@ -1,4 +1,4 @@
-// txf_engine.cpp — the C ABI of include/nstack_txf.h around txf_kernel.hip.
+// txf_engine.cpp — the C ABI of include/nstack_txf.h and include/nstack_txd.h around txf_kernel.hip.
 //
 // Device forms validate and launch. The host form plans on the host (txf_plan.hpp), checks every
 // datagram and the slot capacity, and then runs the double-buffered H2D -> kernel -> D2H pipeline of
@@ -6,12 +6,15 @@
 // a chunk's datagrams are gathered back to back, its frames come back slot by slot and only their
 // F (+ 4) bytes are copied into the caller's arena. No CPU path: a failure is returned, never
 // answered on the host, and the FCS engine's host-batch and fallback counters are not touched.
+// ip_tx_frame_l4_* (nstack_txd.h) are the same two forms with the kernel's L4 variant: the checks,
+// the leases, the plan, the cut and the constants are shared.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
 #include <cstring>
 #include <vector>
 
+#include "../../include/nstack_txd.h"
 #include "../../include/nstack_txf.h"
 #include "fcs_device.hpp"
 #include "fcs_error.hpp"
@@ -24,8 +27,8 @@ using namespace hostpipe;
 
 namespace {
 
-int check_call(uint32_t mtu, uint32_t flags) {
-    if (flags & ~txf::kKnownFlags) return fcs::set_error(EINVAL, "unknown flag bits 0x%x", flags & ~txf::kKnownFlags);
+int check_call(uint32_t mtu, uint32_t flags, uint32_t known = txf::kKnownFlags) {
+    if (flags & ~known) return fcs::set_error(EINVAL, "unknown flag bits 0x%x", flags & ~known);
     if (mtu < txf::kMinMtu || mtu > txf::kMaxMtu)
         return fcs::set_error(EINVAL, "mtu %u outside [%u, %u]", mtu, txf::kMinMtu, txf::kMaxMtu);
     return 0;
@@ -42,10 +45,10 @@ int check_slot(uint32_t mtu, uint32_t flags, uint64_t slot, uint64_t slots) {
 
 // launch_txf with the work counter its rows take their datagrams from, leased from the FCS engine's
 // ring of device `dev` for this launch.
-int launch(txf::FParams &p, int dev, int cus, hipStream_t st) {
+int launch(txf::FParams &p, bool l4, int dev, int cus, hipStream_t st) {
     return fcs::launch_with_counter(dev, (void *)st, [&](unsigned long long *ctr) -> int {
         p.ctr = ctr;
-        HIPTRY(txf::launch_txf(p, cus, st), "launching the txf kernel");
+        HIPTRY(txf::launch_txf(p, l4, cus, st), l4 ? "launching the txd kernel" : "launching the txf kernel");
         return 0;
     });
 }
@@ -65,7 +68,7 @@ const std::vector<BufSpec> kBufs = {{kInBytes + 64, "txf staging"}, {kChunkDgs *
                                     {kChunkDgs * 12, "l2"},         {kOutBytes, "txf frames"}, {kChunkFrames * 4, "flen"}};
 
 // first[0..n] is the host plan; frames of datagrams [i, e) go to slots [first[i], first[e]).
-int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len, const uint8_t *l2, uint64_t n,
+int64_t run_host(bool l4, const uint8_t *dgram, const uint64_t *off, const uint32_t *len, const uint8_t *l2, uint64_t n,
                  uint32_t mtu, uint32_t flags, const uint64_t *first, uint8_t *out, uint64_t slot, uint32_t *flen) {
     int dev = 0, cus = 0;
     int rc = fcs::engine_device0(&dev, &cus);
@@ -120,7 +123,7 @@ int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len,
         p.slots = frames;
         p.flen = s.d<uint32_t>(kFlen);
         p.blob = blob;
-        if ((rc = launch(p, dev, cus, st))) return rc;
+        if ((rc = launch(p, l4, dev, cus, st))) return rc;
         HIPTRY(hipMemcpyAsync(s.h<void>(kOut), s.d<void>(kOut), frames * slot, hipMemcpyDeviceToHost, st), "D2H frames");
         HIPTRY(hipMemcpyAsync(s.h<void>(kFlen), s.d<void>(kFlen), frames * 4, hipMemcpyDeviceToHost, st), "D2H flen");
         s.i0 = first[i];   // the chunk's first slot and its frames
@@ -140,7 +143,81 @@ int64_t run_host(const uint8_t *dgram, const uint64_t *off, const uint32_t *len,
 }
 
 const char *route_name(txf::Route r) {
-    return r == txf::Route::kGeneralFcs ? "general-fcs" : (r == txf::Route::kGeneral ? "general" : "none");
+    switch (r) {
+    case txf::Route::kGeneralFcs: return "general-fcs";
+    case txf::Route::kGeneral: return "general";
+    case txf::Route::kGeneralL4Fcs: return "general-l4-fcs";
+    case txf::Route::kGeneralL4: return "general-l4";
+    default: return "none";
+    }
+}
+
+// The device build of both headers (l4: ip_tx_frame_l4_dev).
+int frame_dev(bool l4, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+              const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first, void *out,
+              uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out, void *stream) {
+    int rc = check_call(mtu, flags, l4 ? txf::kKnownFlagsL4 : txf::kKnownFlags);
+    if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
+    if (n && (!dgram || !off || !len || !l2 || !first || (!out && slots))) return fcs::set_error(EINVAL, "null pointer");
+    int dev = 0, cus = 0;
+    if ((rc = fcs::current_device(&dev, &cus))) return rc;
+    if (n == 0) return 0;
+    txf::FParams p{};
+    p.dg = (uint64_t)dgram;
+    p.lo4 = floor4(p.dg);
+    p.hi4 = ceil4(p.dg + dgram_bytes);
+    p.off = off;
+    p.len = len;
+    p.n = n;
+    p.mtu = mtu;
+    p.flags = flags;
+    p.l2 = reinterpret_cast<const uint8_t *>(l2);
+    p.first = first;
+    p.out = (uint64_t)out;
+    p.slot = slot;
+    p.slots = slots;
+    p.flen = flen;
+    p.status = status;
+    p.fcs = fcs_out;
+    if ((flags & txf::kFlagFcs) && (rc = fcs::device_tables(dev, &p.blob))) return rc;
+    return launch(p, l4, dev, cus, (hipStream_t)stream);
+}
+
+// The host form of both headers (l4: ip_tx_frame_l4_host, whose status words get the L4 bits).
+int64_t frame_host(bool l4, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                   const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out, uint64_t slot,
+                   uint64_t slots, uint32_t *flen, uint32_t *status) {
+    int rc = check_call(mtu, flags, l4 ? txf::kKnownFlagsL4 : txf::kKnownFlags);
+    if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
+    if (n == 0) return 0;
+    if (!dgram || !off || !len || !l2 || (!out && slots)) return fcs::set_error(EINVAL, "null pointer");
+    std::vector<uint64_t> first(n + 1);
+    std::vector<uint32_t> st(n);
+    uint64_t bad = 0;
+    if (txf::plan_batch((const uint8_t *)dgram, dgram_bytes, off, len, n, mtu, flags, st.data(), first.data(), &bad))
+        return fcs::set_error(EINVAL, "datagram %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
+                              (unsigned long long)off[bad], len[bad], (unsigned long long)dgram_bytes);
+    if (first[n] > slots)
+        return fcs::set_error(ENOSPC, "%llu frames need more than the %llu slots given", (unsigned long long)first[n],
+                              (unsigned long long)slots);
+    for (uint64_t i = 0; i < n; i++)
+        if ((first[i + 1] - first[i]) * slot > kOutBytes)
+            return fcs::set_error(EINVAL, "datagram %llu: %llu slots of %llu bytes exceed the %llu-byte host chunk",
+                                  (unsigned long long)i, (unsigned long long)(first[i + 1] - first[i]),
+                                  (unsigned long long)slot, (unsigned long long)kOutBytes);
+    if (l4 && status) {   // nstack_txd.h rule 4, as the kernel states it
+        for (uint64_t i = 0; i < n; i++) {
+            if (st[i] & (txf::kBadHdr | txf::kBadLen)) continue;
+            const uint8_t *h = (const uint8_t *)dgram + off[i];
+            uint32_t fo = 0;
+            st[i] |= txf::l4_fields(h[9], ((uint32_t)h[6] << 8) | h[7], len[i] - (h[0] & 0x0fu) * 4u,
+                                    first[i + 1] > first[i], flags, &fo);
+        }
+    }
+    const int64_t r = run_host(l4, (const uint8_t *)dgram, off, len, reinterpret_cast<const uint8_t *>(l2), n, mtu, flags,
+                               first.data(), (uint8_t *)out, slot, flen);
+    if (r >= 0 && status) std::memcpy(status, st.data(), n * 4);
+    return r;
 }
 
 }  // namespace
@@ -186,61 +263,34 @@ int ether_tx_frame_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *
                        const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first,
                        void *out, uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out,
                        void *stream) {
-    int rc = check_call(mtu, flags);
-    if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
-    if (n && (!dgram || !off || !len || !l2 || !first || (!out && slots))) return fcs::set_error(EINVAL, "null pointer");
-    int dev = 0, cus = 0;
-    if ((rc = fcs::current_device(&dev, &cus))) return rc;
-    if (n == 0) return 0;
-    txf::FParams p{};
-    p.dg = (uint64_t)dgram;
-    p.lo4 = floor4(p.dg);
-    p.hi4 = ceil4(p.dg + dgram_bytes);
-    p.off = off;
-    p.len = len;
-    p.n = n;
-    p.mtu = mtu;
-    p.flags = flags;
-    p.l2 = reinterpret_cast<const uint8_t *>(l2);
-    p.first = first;
-    p.out = (uint64_t)out;
-    p.slot = slot;
-    p.slots = slots;
-    p.flen = flen;
-    p.status = status;
-    p.fcs = fcs_out;
-    if ((flags & txf::kFlagFcs) && (rc = fcs::device_tables(dev, &p.blob))) return rc;
-    return launch(p, dev, cus, (hipStream_t)stream);
+    return frame_dev(false, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
+                     stream);
 }
 
 int64_t ether_tx_frame_host(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
                             const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out,
                             uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status) {
-    int rc = check_call(mtu, flags);
-    if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
-    if (n == 0) return 0;
-    if (!dgram || !off || !len || !l2 || (!out && slots)) return fcs::set_error(EINVAL, "null pointer");
-    std::vector<uint64_t> first(n + 1);
-    std::vector<uint32_t> st(n);
-    uint64_t bad = 0;
-    if (txf::plan_batch((const uint8_t *)dgram, dgram_bytes, off, len, n, mtu, flags, st.data(), first.data(), &bad))
-        return fcs::set_error(EINVAL, "datagram %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
-                              (unsigned long long)off[bad], len[bad], (unsigned long long)dgram_bytes);
-    if (first[n] > slots)
-        return fcs::set_error(ENOSPC, "%llu frames need more than the %llu slots given", (unsigned long long)first[n],
-                              (unsigned long long)slots);
-    for (uint64_t i = 0; i < n; i++)
-        if ((first[i + 1] - first[i]) * slot > kOutBytes)
-            return fcs::set_error(EINVAL, "datagram %llu: %llu slots of %llu bytes exceed the %llu-byte host chunk",
-                                  (unsigned long long)i, (unsigned long long)(first[i + 1] - first[i]),
-                                  (unsigned long long)slot, (unsigned long long)kOutBytes);
-    const int64_t r = run_host((const uint8_t *)dgram, off, len, reinterpret_cast<const uint8_t *>(l2), n, mtu, flags,
-                               first.data(), (uint8_t *)out, slot, flen);
-    if (r >= 0 && status) std::memcpy(status, st.data(), n * 4);
-    return r;
+    return frame_host(false, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
 }
 
 // The kernel the last frame-building launch of this process launched.
 int fcs_debug_txf_last_launch(char *out, uint64_t cap) { return copy_name(route_name(txf::last_launch()), out, cap); }
+
+// ---- include/nstack_txd.h ----
+int ip_tx_frame_l4_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                       const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first,
+                       void *out, uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out,
+                       void *stream) {
+    return frame_dev(true, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
+                     stream);
+}
+
+int64_t ip_tx_frame_l4_host(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                            const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out,
+                            uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status) {
+    return frame_host(true, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
+}
+
+int fcs_debug_txd_last_launch(char *out, uint64_t cap) { return copy_name(route_name(txf::last_launch_l4()), out, cap); }
 
 }  // extern "C"

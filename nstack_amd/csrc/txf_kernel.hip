@@ -34,6 +34,10 @@
 // Reads stay inside [lo4, hi4) of the datagram arena: a chunk window that crosses its edge is
 // loaded dword by dword under a guard (the batch's first and last datagram at most).
 //
+// The walk is written once, frame_walk<FCSW, L4, NT>: txf_kernel is its plain form, txd_kernel the
+// form that also fills every datagram's TCP / UDP / ICMP checksum (include/nstack_txd.h; the comment
+// in front of frame_walk has what it adds).
+//
 // The plan kernels (status and exclusive prefix sums of the frame counts) follow below: counts and
 // block totals, a one-workgroup scan of the totals, the add; no workgroup waits for another.
 #include <hip/hip_runtime.h>
@@ -58,14 +62,37 @@ using rxv::keep_range;
 using rxv::row_get;
 using rxv::row_sum;
 using rxv::swap16;
+using rxv::xor_field;
 
 template <typename T>
 __device__ __forceinline__ void gstore(uint64_t addr, T v) {
     *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
 }
 
+// What the L4 variant (include/nstack_txd.h) keeps besides; empty for the plain framer, whose
+// structures and code stay what they were.
+template <bool L4>
+struct DgL4 {};
+template <>
+struct DgL4<true> {
+    uint32_t ps;       // accumulator start plus pseudo header; 0: nothing is summed
+    uint32_t qf;       // frame position of the checksum field in fragment fidx; 0: no field is written
+    uint32_t fidx;     // the fragment that holds the field, walked last; cnt - 1 without a field
+    uint32_t old;      // the field's content in the datagram (memory grid)
+    uint32_t mac;      // folded sum of frame bytes [0, 14)
+    uint32_t proto;
+};
+template <bool L4>
+struct PosL4 {};
+template <>
+struct PosL4<true> {
+    uint32_t t;        // the frames of the datagram walked before this one
+    bool pre;          // a visit that only sums (a field frame of several segments)
+};
+
 // A datagram that becomes frames (uniform over the row but for the image).
-struct Dg {
+template <bool L4>
+struct Dg : DgL4<L4> {
     uint64_t src;      // the address frame position 0 of fragment 0 maps to: datagram address - 14
     uint64_t slot0;    // its first slot
     uint32_t D, hlen, cnt;
@@ -82,10 +109,11 @@ struct Frame {
     uint32_t f0;       // img0 with this frame's ip_len, ip_foff and checksum
 };
 
-struct Pos {
+template <bool L4>
+struct Pos : PosL4<L4> {
     uint32_t jf, k;    // fragment, segment
     bool act;
-    Dg g;
+    Dg<L4> g;
     Frame fr;
 };
 
@@ -97,12 +125,31 @@ struct Chunk {
     uint32_t r;        // source address of the chunk's first byte & 3
 };
 
-__device__ __forceinline__ int rel_of(const Pos &c, int j) {   // frame position of the chunk's first byte
+template <bool L4>
+__device__ __forceinline__ int rel_of(const Pos<L4> &c, int j) {   // frame position of the chunk's first byte
     return (int)rxv::rel_of(c.fr.F, c.fr.m, c.k, j);
 }
 
-template <bool FCSW, int NT>
-__global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
+// L4 (include/nstack_txd.h): the same walk, plus the TCP / UDP / ICMP checksum of every datagram.
+//   * The sum. A frame's words are summed as they will be stored (rxv::add_sums, the frame END's
+//     word grid; a frame of odd length has its folded sum swapped, as rxv::reduce_sums does for a
+//     whole frame; fragment offsets and 14 + hlen are even, so the frame start's grid is the
+//     segment's). Each lane keeps one running sum per datagram; the row's sum is reduced once, at the
+//     datagram's last frame. What is not segment leaves again: frame bytes [0, 14) of every frame
+//     (their sum is known from the image), nothing for the IP header, whose stored bytes sum to
+//     0xffff, nothing for the padding, which is zero. The field's old content leaves too.
+//   * The order. The value is known after the datagram's last byte but lies near its front, so a
+//     row walks the fragment that holds the field (fo / max) LAST. A field frame of one segment has
+//     all its words in registers when the sum is complete: new ^ old is XORed into them before the
+//     CRC chains run and before anything is stored, as txs_kernel does. A field frame of several
+//     segments (jumbo mtu) is visited twice: the first visit only sums (its loads are the only cost;
+//     no CRC result is kept and nothing is stored), the second is the ordinary one and XORs the
+//     delta into the chunk that holds the field. Every byte is stored once, by the lane that owns
+//     it, with its final value: no late store, and no order between stores is relied on.
+template <bool FCSW, bool L4, int NT>
+__device__ __forceinline__ void frame_walk(FParams p) {
+    using Dg = txf::Dg<L4>;
+    using Pos = txf::Pos<L4>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[FCSW ? fcs::kLdsBytes : 16];
     if (FCSW) fcs::stage_tables<NT>(rxv::tables_of(p.blob), lds);
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
@@ -162,7 +209,14 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
             o.status |= kNoRoom;
             o.cnt = 0u;
         }
-        if (j == 0 && p.status != nullptr) p.status[i] = o.status;
+        uint32_t l4bits = 0u, fo = 0u;
+        if constexpr (L4) {   // proto; segment length, field offset
+            const uint32_t w8 = __builtin_amdgcn_alignbyte(row_get(h0, 3u), e2, r);   // ttl, proto, checksum
+            g.proto = (w8 >> 8) & 0xffu;
+            if (!(o.status & (kBadHdr | kBadLen)))
+                l4bits = l4_fields(g.proto, swap16(w4 >> 16), D - o.hlen, o.cnt != 0u, p.flags, &fo);
+        }
+        if (j == 0 && p.status != nullptr) p.status[i] = o.status | l4bits;
         g.cnt = o.cnt;
         if (!o.cnt) return g;
         g.D = D;
@@ -189,7 +243,33 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
         const int hend = 14 + (int)o.hlen;
         const uint32_t k0 = keep_range(g.img0, 4 * j, 14, hend), k1 = keep_range(g.img1, 64 + 4 * j, 14, hend);
         g.hsum = fold64(row_sum((k0 & 0xffffu) + (k0 >> 16) + (k1 & 0xffffu) + (k1 >> 16)));
+        if constexpr (L4) {
+            const uint32_t m0 = keep_range(g.img0, 4 * j, 0, 14);
+            g.mac = fold64(row_sum((m0 & 0xffffu) + (m0 >> 16)));
+            g.fidx = o.cnt - 1u;
+            if (fo) {
+                // the address words as they lie: frame bytes 26..33 (ones::l4_start has the quirks)
+                const uint32_t d6 = row_get(g.img0, 6u), d7 = row_get(g.img0, 7u), d8 = row_get(g.img0, 8u);
+                uint32_t none = 0u;
+                const bool sum = (l4bits & kL4CsumSet) != 0u;
+                const uint32_t ps = ones::l4_start(g.proto, __builtin_amdgcn_alignbyte(d7, d6, 2u),
+                                                   __builtin_amdgcn_alignbyte(d8, d7, 2u), D - o.hlen, 1u, 0u, none);
+                g.ps = sum ? ps : 0u;
+                const uint32_t q0 = 14u + o.hlen + fo, dw = q0 >> 2;   // the field in the image: 36..90, even
+                const uint32_t v0 = row_get(g.img0, dw & 15u), v1 = row_get(g.img1, dw & 15u);
+                const uint32_t wd = dw < 16u ? v0 : v1;
+                g.old = (q0 & 2u) ? wd >> 16 : wd & 0xffffu;
+                g.fidx = o.max ? fo / o.max : 0u;
+                g.qf = q0 - g.fidx * o.max;
+            }
+        }
         return g;
+    };
+
+    // L4: the fragment a row walks as the datagram's frame number t: the one with the field last.
+    auto frag_at = [&](const Dg &g, uint32_t t) -> uint32_t {
+        if constexpr (L4) return t + 1u == g.cnt ? g.fidx : t + (t >= g.fidx ? 1u : 0u);
+        else return t;
     };
 
     // The row's next datagram that becomes frames; rows with `go` only.
@@ -199,6 +279,7 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
             if (go) {
                 if (cur >= p.n) {
                     n.act = false;
+                    if constexpr (L4) n.pre = false;
                     n.k = 0;
                     n.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
                     go = false;
@@ -209,7 +290,14 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
                         n.jf = 0;
                         n.k = 0;
                         n.act = true;
-                        n.fr = frame_of(g, 0u);
+                        if constexpr (L4) {
+                            n.t = 0;
+                            n.jf = frag_at(g, 0u);
+                            n.fr = frame_of(g, n.jf);
+                            n.pre = g.cnt == 1u && g.qf != 0u && n.fr.m > 1u;
+                        } else {
+                            n.fr = frame_of(g, 0u);
+                        }
                         go = false;
                     }
                 }
@@ -224,9 +312,24 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
             n.k = c.k + 1u;
             if (n.k >= c.fr.m) {
                 n.k = 0;
-                n.jf = c.jf + 1u;
-                if (n.jf >= c.g.cnt) adv = true;
-                else n.fr = frame_of(n.g, n.jf);
+                if constexpr (L4) {
+                    if (c.pre) {
+                        n.pre = false;   // the same frame again, now with the value
+                    } else {
+                        n.t = c.t + 1u;
+                        if (n.t >= c.g.cnt) {
+                            adv = true;
+                        } else {
+                            n.jf = frag_at(n.g, n.t);
+                            n.fr = frame_of(n.g, n.jf);
+                            n.pre = n.t + 1u == n.g.cnt && n.g.qf != 0u && n.fr.m > 1u;
+                        }
+                    }
+                } else {
+                    n.jf = c.jf + 1u;
+                    if (n.jf >= c.g.cnt) adv = true;
+                    else n.fr = frame_of(n.g, n.jf);
+                }
             }
         }
         if (__any(adv)) advance(n, adv);
@@ -263,11 +366,17 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
     // per-frame state, carried over the frame's segments
     uint32_t s = 0;       // CRC register
     uint32_t carry = 0;   // the last word of the previous segment's lane 0 (the bytes in front of lane 15's chunk)
+    // L4: this lane's sum of the frame so far, of the datagram's frames before it (each on its frame
+    // start's grid), and the row's new ^ old of the datagram's field once the sum is complete
+    uint64_t tot = 0, dsum = 0;
+    uint32_t dl4 = 0;
 
     auto process = [&](const Pos &c, const Chunk &ch) {
         const Frame &fr = c.fr;
         const int rel = rel_of(c, j);
-        const bool first = c.k == 0, last = c.act && c.k + 1u == fr.m;
+        bool live = c.act;   // a frame that is built, not only summed
+        if constexpr (L4) live = c.act && !c.pre;
+        const bool first = c.k == 0, last = live && c.k + 1u == fr.m;
         uint32_t d[kChunkWords + 1], w[kChunkWords];   // word i: frame positions rel + 4 i ..
         rxv::unpack(ch.x, ch.x6, d);
         rxv::align_words(d, ch.r, w);
@@ -304,6 +413,30 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
 #pragma unroll
             for (int i = 0; i < kChunkWords; i++) w[i] = fcs::clear_low_bits(w[i], -8 * (rel + 4 * i));
         }
+        // ---- L4: the sums, and at the datagram's last frame the field ----
+        if constexpr (L4) {
+            const bool fend = c.act && c.k + 1u == fr.m;
+            const bool fin = c.act && c.t + 1u == c.g.cnt && c.g.qf != 0u;   // the frame that holds the field
+            const bool again = fin && !c.pre && fr.m > 1u;                    // summed by the visit before
+            uint64_t a = 0, b = 0;
+            rxv::add_sums(w, rel, 0, 0u, a, b);
+            if (first) tot = 0;
+            if (c.act && c.g.ps != 0u && !again) tot += a;
+            if (__any(fend)) {
+                const uint32_t ft = fold64(tot);
+                if (fend) dsum += (fr.F & 1u) ? swap16(ft) : ft;   // the end's grid to the start's
+                if (__any(fend && fin && !again)) {
+                    const rxv::Sums q = rxv::reduce_sums(dsum, 0ull, 0u, false, false);
+                    const uint64_t x = (uint64_t)c.g.ps + q.tot_s + (uint64_t)c.g.cnt * (0xffffu - c.g.mac) + (0xffffu - c.g.old);
+                    uint32_t v = c.g.ps ? ~fold64(x) & 0xffffu : 0u;   // TXD_F_UDP_ZERO: 0, nothing summed
+                    if (v == 0u && c.g.ps != 0u && c.g.proto == 17u) v = 0xffffu;   // RFC 768
+                    if (fend && fin && !again) dl4 = v ^ c.g.old;
+                }
+                if (fend && !c.pre && c.t + 1u == c.g.cnt) dsum = 0;   // the datagram is done
+            }
+            const bool pat = fin && !c.pre;
+            if (__any(pat)) xor_field(w, pat ? (int)c.g.qf - rel : rxv::kNoField, dl4);
+        }
         // ---- CRC over the words as they will be stored ----
         uint32_t crc = 0u;
         if (FCSW) {
@@ -323,7 +456,7 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
             const uint32_t al = __builtin_amdgcn_alignbyte(w[t], t ? w[t - 1] : prevw, 4u - rd);
             dst[t] = rd ? al : w[t];
         }
-        if (c.act) {
+        if (live) {
 #pragma unroll
             for (int q = 0; q < 6; q++) {
                 const uint64_t ad = A0 + 16 * q;
@@ -337,10 +470,10 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
             }
         }
         // the frame's first partial dword: MAC bytes, by byte stores
-        if (__any(c.act && first)) {
+        if (__any(live && first)) {
             const uint32_t mac0 = row_get(fr.f0, 0u);
             const uint32_t nb = (4u - ((uint32_t)fr.fo & 3u)) & 3u;
-            if (c.act && first && (uint32_t)j < nb) gstore<uint8_t>(fr.fo + (uint32_t)j, (uint8_t)(mac0 >> (8 * j)));
+            if (live && first && (uint32_t)j < nb) gstore<uint8_t>(fr.fo + (uint32_t)j, (uint8_t)(mac0 >> (8 * j)));
         }
         // the frame's last partial dword and the FCS, by byte stores; flen and fcs of its slot
         if (__any(last)) {
@@ -357,10 +490,25 @@ __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
     Pos A;
     A.jf = A.k = 0;
     A.act = false;
+    if constexpr (L4) {
+        A.t = 0;
+        A.pre = false;
+    }
     A.g = Dg{};
     A.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
     advance(A, true);
     rxv::two_in_flight<Chunk>(A, next, issue, process);
+}
+
+template <bool FCSW, int NT>
+__global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
+    frame_walk<FCSW, false, NT>(p);
+}
+
+// ip_tx_frame_l4_*: the framer that also fills every datagram's L4 checksum.
+template <bool FCSW, int NT>
+__global__ __launch_bounds__(NT, 1) void txd_kernel(FParams p) {
+    frame_walk<FCSW, true, NT>(p);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -431,20 +579,24 @@ __global__ __launch_bounds__(kPlanThreads) void txf_add_kernel(uint64_t *first, 
 }
 
 namespace {
-std::atomic<int> g_last_route{(int)Route::kNone};
+std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone};
 }
 Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
+Route last_launch_l4() { return (Route)g_last_route_l4.load(std::memory_order_relaxed); }
 
-hipError_t launch_txf(const FParams &p, int cus, hipStream_t st) {
+hipError_t launch_txf(const FParams &p, bool l4, int cus, hipStream_t st) {
     (void)hipGetLastError();   // report this launch's own error, not an earlier call's
     if (!p.n) return hipSuccess;
     if (!p.ctr) return hipErrorInvalidValue;
     const bool fcsw = (p.flags & kFlagFcs) != 0;
-    g_last_route.store((int)(fcsw ? Route::kGeneralFcs : Route::kGeneral), std::memory_order_relaxed);
+    if (l4) g_last_route_l4.store((int)(fcsw ? Route::kGeneralL4Fcs : Route::kGeneralL4), std::memory_order_relaxed);
+    else g_last_route.store((int)(fcsw ? Route::kGeneralFcs : Route::kGeneral), std::memory_order_relaxed);
     // one workgroup per CU, persistent over the datagrams (a quarter-wave per run of datagrams)
     const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
     const int grid = (int)(want < (uint64_t)cus ? want : (uint64_t)cus);
-    if (fcsw) hipLaunchKernelGGL((txf_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    if (l4 && fcsw) hipLaunchKernelGGL((txd_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else if (l4) hipLaunchKernelGGL((txd_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else if (fcsw) hipLaunchKernelGGL((txf_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
     else hipLaunchKernelGGL((txf_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
     return hipGetLastError();
 }

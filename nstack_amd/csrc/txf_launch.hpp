@@ -28,11 +28,13 @@ struct FParams {
 constexpr int kThreads = 512;       // txf_kernel: 8 waves per CU, a quarter-wave per datagram
 constexpr int kPlanThreads = 256;   // the plan kernels: one datagram per thread
 
-enum class Route { kNone, kGeneral, kGeneralFcs };
-Route last_launch();   // what the last launch_txf of this process launched (tests)
+enum class Route { kNone, kGeneral, kGeneralFcs, kGeneralL4, kGeneralL4Fcs };
+Route last_launch();      // what the last launch_txf without l4 of this process launched (tests)
+Route last_launch_l4();   // the same for the launches with l4
 
-// Builds the frames of p.n datagrams on a grid of at most `cus` workgroups; needs p.ctr.
-hipError_t launch_txf(const FParams &p, int cus, hipStream_t st);
+// Builds the frames of p.n datagrams on a grid of at most `cus` workgroups; needs p.ctr. l4: with
+// the L4 checksum of every datagram (include/nstack_txd.h; p.flags may hold kFlagUdpZero).
+hipError_t launch_txf(const FParams &p, bool l4, int cus, hipStream_t st);
 
 // status[i] (may be null) and first[0..n]: counts and per-block totals, the scan of the totals in
 // one workgroup, the add; three launches on `st`. tot holds ceil(n / kPlanThreads) u64 of scratch.

@@ -18,6 +18,10 @@ constexpr uint32_t kWhole = 0x001u, kFragmented = 0x002u, kBadHdr = 0x004u, kBad
                    kDfDrop = 0x020u, kNoRoom = 0x040u;
 constexpr uint32_t kFlagFcs = 1u, kFlagHonorDf = 2u, kFlagL2One = 4u, kKnownFlags = 7u;
 constexpr uint32_t kMinMtu = 76u, kMaxMtu = 65535u;
+// include/nstack_txd.h: framing with L4 checksums takes one flag more and adds these status bits.
+constexpr uint32_t kFlagUdpZero = 0x100u, kKnownFlagsL4 = kKnownFlags | kFlagUdpZero;
+constexpr uint32_t kL4CsumSet = 0x080u, kL4Short = 0x200u;
+constexpr int kProtoShift = 16;
 
 // What one datagram becomes: its status word, frame count, header length and fragment payload unit.
 struct One {
@@ -56,6 +60,20 @@ TXF_HD One plan_fields(uint32_t D, uint32_t vhl, uint32_t ip_len, uint32_t ip_fo
     o.cnt = (D - hlen + o.max - 1u) / o.max;
     o.status = kFragmented;
     return o;
+}
+
+// include/nstack_txd.h rules 2-4 for a datagram that passed framing rules 1-2: the bits its status
+// word gets next to the framing bits, and *fo = the checksum field's offset in the L-byte segment
+// (0: no field is written). framed: the datagram becomes frames; ip_foff in host order.
+TXF_HD uint32_t l4_fields(uint32_t proto, uint32_t ip_foff, uint32_t L, bool framed, uint32_t flags, uint32_t *fo) {
+    const uint32_t bits = proto << kProtoShift;
+    *fo = 0u;
+    if (!framed || (ip_foff & 0x3fffu)) return bits;                       // rule 2
+    const uint32_t need = proto == 6u ? 20u : (proto == 17u ? 8u : (proto == 1u ? 4u : 0u));
+    if (!need) return bits;
+    if (L < need) return bits | kL4Short;                                  // rule 3
+    *fo = proto == 6u ? 16u : (proto == 17u ? 6u : 2u);
+    return (proto == 17u && (flags & kFlagUdpZero)) ? bits : (bits | kL4CsumSet);
 }
 
 // ether_tx_frame_count: rules 3 and 6 alone; 0 for what rule 1 (or the mtu bound) refuses.

@@ -52,12 +52,12 @@ using fcs::kGroup;
 using rxv::Chunk;
 using rxv::fold64;
 using rxv::Frame;
+using rxv::kNoField;
 using rxv::Pos;
 using rxv::row_get;
 using rxv::RParams;
 using rxv::swap16;
-
-constexpr int kNoField = 1 << 20;   // a chunk byte offset no chunk has
+using rxv::xor_field;
 
 // What a frame's header decided before its first chunk is summed (uniform over the frame's lanes).
 struct THdr {
@@ -122,23 +122,6 @@ __device__ __forceinline__ THdr decode(const Frame &fr, const Chunk &ch, int j, 
     }
     h.sums = rxv::header_sums(ch, j, r, h.che);
     return h;
-}
-
-// XORs the 16-bit value `delta` (its low byte first) into the chunk words at chunk byte offset b,
-// by bytes: b = -1 reaches only the second byte (word 0), b = 95 only the first; any other b outside
-// [0, 95) does nothing. Only the 6-word blocks some lane of the wave has such bytes in are touched.
-__device__ __forceinline__ void xor_field(uint32_t (&w)[kChunkWords], int b, uint32_t delta) {
-    const bool in = b >= -1 && b < kChunkBytes;
-    const int iw = b >> 2;   // -1 for b = -1
-    const uint64_t P = (uint64_t)delta << (8 * (b & 3));
-    const uint32_t P0 = in ? (uint32_t)P : 0u, P1 = in ? (uint32_t)(P >> 32) : 0u;
-#pragma unroll
-    for (int blk = 0; blk < 4; blk++) {
-        if (__any(in && iw + 1 >= 6 * blk && iw < 6 * blk + 6)) {
-#pragma unroll
-            for (int i = 6 * blk; i < 6 * blk + 6; i++) w[i] ^= (i == iw ? P0 : 0u) ^ (i == iw + 1 ? P1 : 0u);
-        }
-    }
 }
 
 // The values to write, from the reduced sums (row-uniform).
