@@ -36,7 +36,9 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "rx_reasm_l4_dev", "rx_reasm_l4_host", "rxd_last_launch", "RXD_EXPORTS", "RXD_NO_ROOM", "RXD_L4_CHECKED",
            "RXD_L4_BAD_CSUM", "RXD_L4_SHORT", "RXD_PROTO_SHIFT",
            "tx_frame_l4_dev", "tx_frame_l4_host", "txd_last_launch", "TXD_EXPORTS", "TXD_F_UDP_ZERO", "TXD_L4_CSUM_SET",
-           "TXD_L4_SHORT", "TXD_PROTO_SHIFT"]
+           "TXD_L4_SHORT", "TXD_PROTO_SHIFT",
+           "tx_tso_count", "tx_tso_plan_dev", "tx_tso_dev", "tx_tso_host", "tso_last_launch", "TSO_EXPORTS",
+           "TSO_F_ID_FIXED", "TSO_F_MSS_ONE", "TSO_SEGMENTED"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -105,6 +107,11 @@ TXD_EXPORTS = ["ip_tx_frame_l4_dev", "ip_tx_frame_l4_host", "fcs_debug_txd_last_
 TXD_F_UDP_ZERO = 0x100
 TXD_L4_CSUM_SET, TXD_L4_SHORT = 0x080, 0x200
 TXD_PROTO_SHIFT = 16
+
+# include/nstack_tso.h — one-pass TCP segmentation (its own list, as TXD_EXPORTS)
+TSO_EXPORTS = ["ip_tx_tso_count", "ip_tx_tso_plan_dev", "ip_tx_tso_dev", "ip_tx_tso_host", "fcs_debug_tso_last_launch"]
+TSO_F_ID_FIXED, TSO_F_MSS_ONE = 0x200, 0x400
+TSO_SEGMENTED = 0x400
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -256,6 +263,11 @@ def _bind(path: str) -> ctypes.CDLL:
         "ip_tx_frame_l4_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
         "ip_tx_frame_l4_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
         "fcs_debug_txd_last_launch": (i32, [c.c_char_p, u64]),
+        "ip_tx_tso_count": (u32, [u32, u32, u32, u32, u32, u32, u32]),
+        "ip_tx_tso_plan_dev": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, vp]),
+        "ip_tx_tso_dev": (i32, [vp, u64, vp, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64, vp, vp, vp, vp]),
+        "ip_tx_tso_host": (c.c_int64, [vp, u64, vp, vp, vp, vp, u64, u32, u32, vp, u64, u64, vp, vp]),
+        "fcs_debug_tso_last_launch": (i32, [c.c_char_p, u64]),
         "ether_rx_reasm_plan_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "ether_rx_reasm_plan_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ether_rx_reasm_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp]),
@@ -864,6 +876,50 @@ def txd_last_launch() -> str:
     """The kernel the last launch of tx_frame_l4_dev / tx_frame_l4_host of this process launched."""
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_txd_last_launch(buf, 32), "fcs_debug_txd_last_launch")
+    return buf.value.decode()
+
+
+# ---- one-pass TCP segmentation (include/nstack_tso.h) ----
+def tx_tso_count(dgram_len: int, hlen: int, thl: int, tcp_flags: int, ip_foff: int, mss: int, mtu: int) -> int:
+    """Frames a TCP datagram becomes when it is segmented at this mss (0: as large as the mtu allows) and
+    mtu (host arithmetic); 0 when it is not segmented and follows tx_frame_l4_* instead."""
+    return int(load().ip_tx_tso_count(_u32(dgram_len, "dgram_len"), _u32(hlen, "hlen"), _u32(thl, "thl"),
+                                      _u32(tcp_flags, "tcp_flags"), _u32(ip_foff, "ip_foff"), _u32(mss, "mss"),
+                                      _u32(mtu, "mtu")))
+
+
+def tx_tso_plan_dev(dgram, dgram_bytes: int, off, length, mss, n: int, mtu: int, first, flags: int = 0, status=None,
+                    stream=None) -> None:
+    """tx_frame_plan_dev with eligible TCP datagrams counted in MSS segments: mss (u16 per datagram, one
+    with TSO_F_MSS_ONE, or None), status[i] the whole status word. Device arrays; asynchronous on `stream`."""
+    _check(load().ip_tx_tso_plan_dev(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(mss), n, _u32(mtu, "mtu"),
+                                     _u32(flags, "flags"), _ptr(status), _ptr(first), _stream(stream)),
+           "ip_tx_tso_plan_dev")
+
+
+def tx_tso_dev(dgram, dgram_bytes: int, off, length, l2, mss, n: int, mtu: int, first, out, slot: int, slots: int,
+               flags: int = TXF_F_FCS, flen=None, status=None, fcs=None, stream=None) -> None:
+    """tx_frame_l4_dev in which an eligible TCP datagram whose payload exceeds its mss leaves as TCP segments
+    with their own headers and checksums (TSO_SEGMENTED). Device arrays; asynchronous on `stream`."""
+    _check(load().ip_tx_tso_dev(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), _ptr(mss), n,
+                                _u32(mtu, "mtu"), _u32(flags, "flags"), _ptr(first), _ptr(out), slot, slots, _ptr(flen),
+                                _ptr(status), _ptr(fcs), _stream(stream)),
+           "ip_tx_tso_dev")
+
+
+def tx_tso_host(dgram, dgram_bytes: int, off, length, l2, mss, n: int, mtu: int, out, slot: int, slots: int,
+                flags: int = TXF_F_FCS, flen=None, status=None) -> int:
+    """Host form: tx_frame_l4_host with TCP segmentation. Returns the number of frames."""
+    return _check(load().ip_tx_tso_host(_ptr(dgram), dgram_bytes, _ptr(off), _ptr(length), _ptr(l2), _ptr(mss), n,
+                                        _u32(mtu, "mtu"), _u32(flags, "flags"), _ptr(out), slot, slots, _ptr(flen),
+                                        _ptr(status)),
+                  "ip_tx_tso_host")
+
+
+def tso_last_launch() -> str:
+    """The kernel the last launch of tx_tso_dev / tx_tso_host of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_tso_last_launch(buf, 32), "fcs_debug_tso_last_launch")
     return buf.value.decode()
 
 

@@ -7,13 +7,15 @@
 // F (+ 4) bytes are copied into the caller's arena. No CPU path: a failure is returned, never
 // answered on the host, and the FCS engine's host-batch and fallback counters are not touched.
 // ip_tx_frame_l4_* (nstack_txd.h) are the same two forms with the kernel's L4 variant: the checks,
-// the leases, the plan, the cut and the constants are shared.
+// the leases, the plan, the cut and the constants are shared. ip_tx_tso_* (nstack_tso.h) are the same
+// again with the segmenting variant, the plan of tso_plan.hpp and an mss array staged per chunk.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
 #include <cstring>
 #include <vector>
 
+#include "../../include/nstack_tso.h"
 #include "../../include/nstack_txd.h"
 #include "../../include/nstack_txf.h"
 #include "fcs_device.hpp"
@@ -24,6 +26,7 @@
 static_assert(sizeof(txf_l2) == 12, "the MAC record is 12 bytes");
 
 using namespace hostpipe;
+using txf::Mode;
 
 namespace {
 
@@ -45,10 +48,12 @@ int check_slot(uint32_t mtu, uint32_t flags, uint64_t slot, uint64_t slots) {
 
 // launch_txf with the work counter its rows take their datagrams from, leased from the FCS engine's
 // ring of device `dev` for this launch.
-int launch(txf::FParams &p, bool l4, int dev, int cus, hipStream_t st) {
+int launch(txf::FParams &p, Mode mode, int dev, int cus, hipStream_t st) {
     return fcs::launch_with_counter(dev, (void *)st, [&](unsigned long long *ctr) -> int {
         p.ctr = ctr;
-        HIPTRY(txf::launch_txf(p, l4, cus, st), l4 ? "launching the txd kernel" : "launching the txf kernel");
+        HIPTRY(txf::launch_txf(p, mode, cus, st), mode == Mode::kTso  ? "launching the tso kernel"
+                                                  : mode == Mode::kL4 ? "launching the txd kernel"
+                                                                      : "launching the txf kernel");
         return 0;
     });
 }
@@ -63,13 +68,14 @@ constexpr uint64_t kChunkFrames = 1ull << 20;
 constexpr int kDepth = 2;
 
 struct TxfPipe;   // names this engine's pipelines (host_pipe.hpp)
-enum { kIn, kOff, kLen, kL2, kOut, kFlen };   // kOff: off[kChunkDgs], then first[kChunkDgs]
-const std::vector<BufSpec> kBufs = {{kInBytes + 64, "txf staging"}, {kChunkDgs * 16, "off"},   {kChunkDgs * 4, "len"},
+enum { kIn, kOff, kLen, kL2, kOut, kFlen };   // kOff: off[kChunkDgs], then first[kChunkDgs]; kLen: len, then the u16 mss
+const std::vector<BufSpec> kBufs = {{kInBytes + 64, "txf staging"}, {kChunkDgs * 16, "off"},   {kChunkDgs * 6, "len, mss"},
                                     {kChunkDgs * 12, "l2"},         {kOutBytes, "txf frames"}, {kChunkFrames * 4, "flen"}};
 
 // first[0..n] is the host plan; frames of datagrams [i, e) go to slots [first[i], first[e]).
-int64_t run_host(bool l4, const uint8_t *dgram, const uint64_t *off, const uint32_t *len, const uint8_t *l2, uint64_t n,
-                 uint32_t mtu, uint32_t flags, const uint64_t *first, uint8_t *out, uint64_t slot, uint32_t *flen) {
+int64_t run_host(Mode mode, const uint8_t *dgram, const uint64_t *off, const uint32_t *len, const uint8_t *l2,
+                 const uint16_t *mss, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first, uint8_t *out,
+                 uint64_t slot, uint32_t *flen) {
     int dev = 0, cus = 0;
     int rc = fcs::engine_device0(&dev, &cus);
     if (rc) return rc;
@@ -107,6 +113,14 @@ int64_t run_host(bool l4, const uint8_t *dgram, const uint64_t *off, const uint3
         HIPTRY(hipMemcpyAsync(d_off + kChunkDgs, h_off + kChunkDgs, np * 8, hipMemcpyHostToDevice, st), "H2D first");
         HIPTRY(hipMemcpyAsync(s.d<void>(kLen), s.h<void>(kLen), np * 4, hipMemcpyHostToDevice, st), "H2D len");
         HIPTRY(hipMemcpyAsync(s.d<void>(kL2), s.h<void>(kL2), nl2 * 12, hipMemcpyHostToDevice, st), "H2D l2");
+        const uint16_t *d_mss = nullptr;   // nstack_tso.h: the chunk's mss entries behind its len[]
+        if (mss) {
+            const uint64_t nm = (flags & txf::kFlagMssOne) ? 1 : np;
+            uint16_t *h_mss = reinterpret_cast<uint16_t *>(s.h<uint32_t>(kLen) + kChunkDgs);
+            std::memcpy(h_mss, mss + ((flags & txf::kFlagMssOne) ? 0 : i), nm * 2);
+            d_mss = reinterpret_cast<const uint16_t *>(s.d<uint32_t>(kLen) + kChunkDgs);
+            HIPTRY(hipMemcpyAsync((void *)d_mss, h_mss, nm * 2, hipMemcpyHostToDevice, st), "H2D mss");
+        }
         txf::FParams p{};
         p.dg = (uint64_t)s.d<void>(kIn);
         p.lo4 = floor4(p.dg);
@@ -123,7 +137,8 @@ int64_t run_host(bool l4, const uint8_t *dgram, const uint64_t *off, const uint3
         p.slots = frames;
         p.flen = s.d<uint32_t>(kFlen);
         p.blob = blob;
-        if ((rc = launch(p, l4, dev, cus, st))) return rc;
+        p.mss = d_mss;
+        if ((rc = launch(p, mode, dev, cus, st))) return rc;
         HIPTRY(hipMemcpyAsync(s.h<void>(kOut), s.d<void>(kOut), frames * slot, hipMemcpyDeviceToHost, st), "D2H frames");
         HIPTRY(hipMemcpyAsync(s.h<void>(kFlen), s.d<void>(kFlen), frames * 4, hipMemcpyDeviceToHost, st), "D2H flen");
         s.i0 = first[i];   // the chunk's first slot and its frames
@@ -148,15 +163,22 @@ const char *route_name(txf::Route r) {
     case txf::Route::kGeneral: return "general";
     case txf::Route::kGeneralL4Fcs: return "general-l4-fcs";
     case txf::Route::kGeneralL4: return "general-l4";
+    case txf::Route::kTsoFcs: return "tso-fcs";
+    case txf::Route::kTso: return "tso";
     default: return "none";
     }
 }
 
-// The device build of both headers (l4: ip_tx_frame_l4_dev).
-int frame_dev(bool l4, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+uint32_t known_flags(Mode mode) {
+    return mode == Mode::kTso ? txf::kKnownFlagsTso : (mode == Mode::kL4 ? txf::kKnownFlagsL4 : txf::kKnownFlags);
+}
+
+// The device build of the three headers (Mode::kL4: ip_tx_frame_l4_dev; Mode::kTso: ip_tx_tso_dev, mss
+// device memory or null).
+int frame_dev(Mode mode, const uint16_t *mss, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
               const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first, void *out,
               uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out, void *stream) {
-    int rc = check_call(mtu, flags, l4 ? txf::kKnownFlagsL4 : txf::kKnownFlags);
+    int rc = check_call(mtu, flags, known_flags(mode));
     if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
     if (n && (!dgram || !off || !len || !l2 || !first || (!out && slots))) return fcs::set_error(EINVAL, "null pointer");
     int dev = 0, cus = 0;
@@ -179,22 +201,28 @@ int frame_dev(bool l4, const void *dgram, uint64_t dgram_bytes, const uint64_t *
     p.flen = flen;
     p.status = status;
     p.fcs = fcs_out;
+    p.mss = mss;
     if ((flags & txf::kFlagFcs) && (rc = fcs::device_tables(dev, &p.blob))) return rc;
-    return launch(p, l4, dev, cus, (hipStream_t)stream);
+    return launch(p, mode, dev, cus, (hipStream_t)stream);
 }
 
-// The host form of both headers (l4: ip_tx_frame_l4_host, whose status words get the L4 bits).
-int64_t frame_host(bool l4, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+// The host form of the three headers (Mode::kL4: ip_tx_frame_l4_host, whose status words get the L4
+// bits; Mode::kTso: ip_tx_tso_host, planned by tso_plan.hpp, mss host memory or null).
+int64_t frame_host(Mode mode, const uint16_t *mss, const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
                    const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out, uint64_t slot,
                    uint64_t slots, uint32_t *flen, uint32_t *status) {
-    int rc = check_call(mtu, flags, l4 ? txf::kKnownFlagsL4 : txf::kKnownFlags);
+    int rc = check_call(mtu, flags, known_flags(mode));
     if (rc || (rc = check_slot(mtu, flags, slot, slots))) return rc;
     if (n == 0) return 0;
     if (!dgram || !off || !len || !l2 || (!out && slots)) return fcs::set_error(EINVAL, "null pointer");
     std::vector<uint64_t> first(n + 1);
     std::vector<uint32_t> st(n);
     uint64_t bad = 0;
-    if (txf::plan_batch((const uint8_t *)dgram, dgram_bytes, off, len, n, mtu, flags, st.data(), first.data(), &bad))
+    const int prc = mode == Mode::kTso ? txf::tso_plan_batch((const uint8_t *)dgram, dgram_bytes, off, len, mss, n, mtu, flags,
+                                                             st.data(), first.data(), &bad)
+                                       : txf::plan_batch((const uint8_t *)dgram, dgram_bytes, off, len, n, mtu, flags,
+                                                         st.data(), first.data(), &bad);
+    if (prc)
         return fcs::set_error(EINVAL, "datagram %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
                               (unsigned long long)off[bad], len[bad], (unsigned long long)dgram_bytes);
     if (first[n] > slots)
@@ -205,7 +233,7 @@ int64_t frame_host(bool l4, const void *dgram, uint64_t dgram_bytes, const uint6
             return fcs::set_error(EINVAL, "datagram %llu: %llu slots of %llu bytes exceed the %llu-byte host chunk",
                                   (unsigned long long)i, (unsigned long long)(first[i + 1] - first[i]),
                                   (unsigned long long)slot, (unsigned long long)kOutBytes);
-    if (l4 && status) {   // nstack_txd.h rule 4, as the kernel states it
+    if (mode == Mode::kL4 && status) {   // nstack_txd.h rule 4, as the kernel states it
         for (uint64_t i = 0; i < n; i++) {
             if (st[i] & (txf::kBadHdr | txf::kBadLen)) continue;
             const uint8_t *h = (const uint8_t *)dgram + off[i];
@@ -214,22 +242,17 @@ int64_t frame_host(bool l4, const void *dgram, uint64_t dgram_bytes, const uint6
                                     first[i + 1] > first[i], flags, &fo);
         }
     }
-    const int64_t r = run_host(l4, (const uint8_t *)dgram, off, len, reinterpret_cast<const uint8_t *>(l2), n, mtu, flags,
-                               first.data(), (uint8_t *)out, slot, flen);
+    const int64_t r = run_host(mode, (const uint8_t *)dgram, off, len, reinterpret_cast<const uint8_t *>(l2), mss, n, mtu,
+                               flags, first.data(), (uint8_t *)out, slot, flen);
     if (r >= 0 && status) std::memcpy(status, st.data(), n * 4);
     return r;
 }
 
-}  // namespace
-
-extern "C" {
-
-uint32_t ether_tx_frame_count(uint32_t D, uint32_t hlen, uint32_t mtu) { return txf::frame_count(D, hlen, mtu); }
-
-int ether_tx_frame_plan_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
-                            uint64_t n, uint32_t mtu, uint32_t flags, uint32_t *status, uint64_t *first,
-                            void *stream) {
-    int rc = check_call(mtu, flags);
+// The device plan of nstack_txf.h, or (tso: with mss, device memory or null) of nstack_tso.h.
+int plan_dev(bool tso, const uint16_t *mss, const void *dgram, uint64_t dgram_bytes, const uint64_t *off,
+             const uint32_t *len, uint64_t n, uint32_t mtu, uint32_t flags, uint32_t *status, uint64_t *first,
+             void *stream) {
+    int rc = check_call(mtu, flags, tso ? txf::kKnownFlagsTso : txf::kKnownFlags);
     if (rc) return rc;
     if (!first || (n && (!dgram || !off || !len))) return fcs::set_error(EINVAL, "null pointer");
     int dev = 0, cus = 0;
@@ -248,29 +271,42 @@ int ether_tx_frame_plan_dev(const void *dgram, uint64_t dgram_bytes, const uint6
     p.n = n;
     p.mtu = mtu;
     p.flags = flags;
+    p.mss = mss;
     // the block totals: scratch that lives on the stream, between the three launches
     const uint64_t nb = (n + txf::kPlanThreads - 1) / txf::kPlanThreads;
     uint64_t *tot = nullptr;
     HIPTRY(hipMallocAsync((void **)&tot, nb * 8, st), "hipMallocAsync(block totals)");
-    const hipError_t e = txf::launch_plan(p, status, first, tot, st);
+    const hipError_t e = tso ? txf::launch_plan_tso(p, status, first, tot, st) : txf::launch_plan(p, status, first, tot, st);
     const hipError_t e2 = hipFreeAsync(tot, st);
     HIPTRY(e, "launching the txf plan kernels");
     HIPTRY(e2, "hipFreeAsync(block totals)");
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+uint32_t ether_tx_frame_count(uint32_t D, uint32_t hlen, uint32_t mtu) { return txf::frame_count(D, hlen, mtu); }
+
+int ether_tx_frame_plan_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                            uint64_t n, uint32_t mtu, uint32_t flags, uint32_t *status, uint64_t *first,
+                            void *stream) {
+    return plan_dev(false, nullptr, dgram, dgram_bytes, off, len, n, mtu, flags, status, first, stream);
+}
+
 int ether_tx_frame_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
                        const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first,
                        void *out, uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out,
                        void *stream) {
-    return frame_dev(false, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
+    return frame_dev(Mode::kPlain, nullptr, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
                      stream);
 }
 
 int64_t ether_tx_frame_host(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
                             const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out,
                             uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status) {
-    return frame_host(false, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
+    return frame_host(Mode::kPlain, nullptr, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
 }
 
 // The kernel the last frame-building launch of this process launched.
@@ -281,16 +317,44 @@ int ip_tx_frame_l4_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *
                        const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, const uint64_t *first,
                        void *out, uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status, uint32_t *fcs_out,
                        void *stream) {
-    return frame_dev(true, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
+    return frame_dev(Mode::kL4, nullptr, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status, fcs_out,
                      stream);
 }
 
 int64_t ip_tx_frame_l4_host(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
                             const struct txf_l2 *l2, uint64_t n, uint32_t mtu, uint32_t flags, void *out,
                             uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status) {
-    return frame_host(true, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
+    return frame_host(Mode::kL4, nullptr, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
 }
 
 int fcs_debug_txd_last_launch(char *out, uint64_t cap) { return copy_name(route_name(txf::last_launch_l4()), out, cap); }
+
+// ---- include/nstack_tso.h ----
+uint32_t ip_tx_tso_count(uint32_t D, uint32_t hlen, uint32_t thl, uint32_t tcp_flags, uint32_t ip_foff, uint32_t mss,
+                         uint32_t mtu) {
+    return txf::tso_count(D, hlen, thl, tcp_flags, ip_foff, mss, mtu);
+}
+
+int ip_tx_tso_plan_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                       const uint16_t *mss, uint64_t n, uint32_t mtu, uint32_t flags, uint32_t *status, uint64_t *first,
+                       void *stream) {
+    return plan_dev(true, mss, dgram, dgram_bytes, off, len, n, mtu, flags, status, first, stream);
+}
+
+int ip_tx_tso_dev(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                  const struct txf_l2 *l2, const uint16_t *mss, uint64_t n, uint32_t mtu, uint32_t flags,
+                  const uint64_t *first, void *out, uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status,
+                  uint32_t *fcs_out, void *stream) {
+    return frame_dev(Mode::kTso, mss, dgram, dgram_bytes, off, len, l2, n, mtu, flags, first, out, slot, slots, flen, status,
+                     fcs_out, stream);
+}
+
+int64_t ip_tx_tso_host(const void *dgram, uint64_t dgram_bytes, const uint64_t *off, const uint32_t *len,
+                       const struct txf_l2 *l2, const uint16_t *mss, uint64_t n, uint32_t mtu, uint32_t flags, void *out,
+                       uint64_t slot, uint64_t slots, uint32_t *flen, uint32_t *status) {
+    return frame_host(Mode::kTso, mss, dgram, dgram_bytes, off, len, l2, n, mtu, flags, out, slot, slots, flen, status);
+}
+
+int fcs_debug_tso_last_launch(char *out, uint64_t cap) { return copy_name(route_name(txf::last_launch_tso()), out, cap); }
 
 }  // extern "C"

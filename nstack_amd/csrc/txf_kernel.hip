@@ -34,9 +34,10 @@
 // Reads stay inside [lo4, hi4) of the datagram arena: a chunk window that crosses its edge is
 // loaded dword by dword under a guard (the batch's first and last datagram at most).
 //
-// The walk is written once, frame_walk<FCSW, L4, NT>: txf_kernel is its plain form, txd_kernel the
-// form that also fills every datagram's TCP / UDP / ICMP checksum (include/nstack_txd.h; the comment
-// in front of frame_walk has what it adds).
+// The walk is written once, frame_walk<FCSW, Mode, NT>: txf_kernel is its plain form, txd_kernel the
+// form that also fills every datagram's TCP / UDP / ICMP checksum (include/nstack_txd.h), tso_kernel
+// that form with eligible TCP datagrams cut into MSS segments instead of fragments
+// (include/nstack_tso.h); the comment in front of frame_walk has what each adds.
 //
 // The plan kernels (status and exclusive prefix sums of the frame counts) follow below: counts and
 // block totals, a one-workgroup scan of the totals, the add; no workgroup waits for another.
@@ -90,9 +91,30 @@ struct PosL4<true> {
     bool pre;          // a visit that only sums (a field frame of several segments)
 };
 
+// What the segmenting variant (include/nstack_tso.h) keeps besides; empty for the other two.
+template <bool TSO>
+struct DgTso {};
+template <>
+struct DgTso<true> {
+    uint32_t thl;      // the TCP header's bytes; 0: not segmented, the datagram takes the L4 path
+    uint32_t hb;       // the bytes of every frame that come from the image behind the MAC header: hlen (+ thl)
+    uint32_t seq0;     // the datagram's sequence number (host order)
+    uint32_t id0;      // its ip_id (host order)
+    uint32_t tfl;      // its TCP flags byte
+};
+template <bool TSO>
+struct FrameTso {};
+template <>
+struct FrameTso<true> {
+    uint32_t f1;       // img1 with this frame's TCP fields (hlen >= 32 puts them there)
+};
+
+constexpr bool l4_of(Mode m) { return m != Mode::kPlain; }
+constexpr bool tso_of(Mode m) { return m == Mode::kTso; }
+
 // A datagram that becomes frames (uniform over the row but for the image).
-template <bool L4>
-struct Dg : DgL4<L4> {
+template <Mode M>
+struct Dg : DgL4<l4_of(M)>, DgTso<tso_of(M)> {
     uint64_t src;      // the address frame position 0 of fragment 0 maps to: datagram address - 14
     uint64_t slot0;    // its first slot
     uint32_t D, hlen, cnt;
@@ -102,19 +124,27 @@ struct Dg : DgL4<L4> {
     uint32_t keep;     // the datagram's own ip_len | ip_foff << 16, as they lie in memory (TXF_WHOLE)
 };
 
-struct Frame {
+template <Mode M>
+struct Frame : FrameTso<tso_of(M)> {
     uint64_t fo;       // address of the frame's first byte
     uint64_t src;      // the address frame position 0 maps to in the datagram arena
     uint32_t F, I, m;  // frame bytes, IP bytes, segments
     uint32_t f0;       // img0 with this frame's ip_len, ip_foff and checksum
 };
 
-template <bool L4>
-struct Pos : PosL4<L4> {
+template <Mode M>
+__device__ __forceinline__ Frame<M> idle_frame() {   // what a row without work holds: one segment of nothing
+    Frame<M> f{};
+    f.m = 1u;
+    return f;
+}
+
+template <Mode M>
+struct Pos : PosL4<l4_of(M)> {
     uint32_t jf, k;    // fragment, segment
     bool act;
-    Dg<L4> g;
-    Frame fr;
+    Dg<M> g;
+    Frame<M> fr;
 };
 
 constexpr uint64_t kRun = 8;   // datagrams a row takes from the work counter at a time
@@ -125,9 +155,17 @@ struct Chunk {
     uint32_t r;        // source address of the chunk's first byte & 3
 };
 
-template <bool L4>
-__device__ __forceinline__ int rel_of(const Pos<L4> &c, int j) {   // frame position of the chunk's first byte
+template <Mode M>
+__device__ __forceinline__ int rel_of(const Pos<M> &c, int j) {   // frame position of the chunk's first byte
     return (int)rxv::rel_of(c.fr.F, c.fr.m, c.k, j);
+}
+
+// Mode::kTso: dword d of a segment's header image part that changes from frame to frame, T = 14 + hlen
+// the frame position of the TCP header (T & 3 == 2): tcp_seqno at T + 4 (sw: its four bytes as they
+// lie), the flags byte at T + 13, the checksum at T + 16. All ones in, the mask of these fields out.
+__device__ __forceinline__ uint32_t tcp_words(uint32_t d, uint32_t T, uint32_t sw, uint32_t fl, uint32_t cs) {
+    const uint32_t ds = (T + 4u) >> 2, df = (T + 13u) >> 2, dc = (T + 16u) >> 2;
+    return (d == ds ? sw << 16 : 0u) | (d == ds + 1u ? sw >> 16 : 0u) | (d == df ? fl << 24 : 0u) | (d == dc ? cs << 16 : 0u);
 }
 
 // L4 (include/nstack_txd.h): the same walk, plus the TCP / UDP / ICMP checksum of every datagram.
@@ -146,10 +184,34 @@ __device__ __forceinline__ int rel_of(const Pos<L4> &c, int j) {   // frame posi
 //     no CRC result is kept and nothing is stored), the second is the ordinary one and XORs the
 //     delta into the chunk that holds the field. Every byte is stored once, by the lane that owns
 //     it, with its final value: no late store, and no order between stores is relied on.
-template <bool FCSW, bool L4, int NT>
+//
+// TSO (include/nstack_tso.h): the L4 walk, in which an eligible TCP datagram whose payload exceeds its
+// MSS m is cut into frames of m payload bytes instead of fragments. What differs for such a datagram:
+//   * The image holds the TCP header too (hb = hlen + thl bytes behind the MAC header), with ip_len,
+//     ip_id, the IP checksum, tcp_seqno, the flags byte and the TCP checksum zero. frame_of ORs the
+//     frame's own values into BOTH image dwords (f0, f1): from hlen 32 on the TCP fields lie in dwords
+//     16 and up. The payload of frame s starts s m bytes further on in the datagram.
+//   * The checksum belongs to the frame. Every frame is a field frame: its sum is reduced at its own
+//     end (on its own grid: m may be odd, so the parity swap is per frame), the pseudo header takes
+//     the frame's thl + plen, and the value is XORed into the words before the CRC chains and the
+//     stores. Frames are walked in order. A frame of several 1536-byte segments takes the sum-only
+//     first visit: at mtu > 1522 that is every full frame of a segmented datagram.
+// Every statement of this mode sits under `if constexpr (TSO)`.
+template <bool FCSW, Mode M, int NT>
 __device__ __forceinline__ void frame_walk(FParams p) {
-    using Dg = txf::Dg<L4>;
-    using Pos = txf::Pos<L4>;
+    constexpr bool L4 = l4_of(M), TSO = tso_of(M);
+    using Dg = txf::Dg<M>;
+    using Pos = txf::Pos<M>;
+    using Frame = txf::Frame<M>;
+    // TSO: the datagram is segmented; the bytes the image gives every frame behind the MAC header
+    auto seg_of = [](const Dg &g) -> bool {
+        if constexpr (TSO) return g.thl != 0u;
+        else return false;
+    };
+    auto hb_of = [](const Dg &g) -> uint32_t {
+        if constexpr (TSO) return g.hb;
+        else return g.hlen;
+    };
     __shared__ __attribute__((aligned(16))) uint8_t lds[FCSW ? fcs::kLdsBytes : 16];
     if (FCSW) fcs::stage_tables<NT>(rxv::tables_of(p.blob), lds);
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
@@ -175,14 +237,33 @@ __device__ __forceinline__ void frame_walk(FParams p) {
     auto frame_of = [&](const Dg &g, uint32_t jf) -> Frame {
         Frame f;
         const bool whole = g.max == 0u;
-        const uint32_t B = g.D - g.hlen, at = jf * g.max;
+        const uint32_t hb = hb_of(g);
+        const uint32_t B = g.D - hb, at = jf * g.max;
         const uint32_t plen = B - at < g.max ? B - at : g.max;
-        f.I = whole ? g.D : g.hlen + plen;
+        f.I = whole ? g.D : hb + plen;
         const uint32_t fo16 = (jf + 1u < g.cnt ? 0x2000u : 0u) | (at >> 3);
         const uint32_t lenw = whole ? (g.keep & 0xffffu) : swap16(f.I);
-        const uint32_t foffw = whole ? (g.keep >> 16) : swap16(fo16);
-        const uint32_t csum = ~fold64((uint64_t)g.hsum + lenw + foffw) & 0xffffu;   // rule 7
-        f.f0 = g.img0 | (j == 4 ? lenw : 0u) | (j == 5 ? foffw : 0u) | (j == 6 ? csum : 0u);
+        uint32_t foffw = whole ? (g.keep >> 16) : swap16(fo16);
+        uint32_t idw = 0u;   // TSO: a segment's own ip_id; its ip_foff stays as it lies
+        if constexpr (TSO) {
+            if (seg_of(g)) {
+                foffw = g.keep >> 16;
+                idw = swap16((g.id0 + ((p.flags & kFlagIdFixed) ? 0u : jf)) & 0xffffu);
+            }
+        }
+        const uint32_t csum = ~fold64((uint64_t)g.hsum + lenw + foffw + idw) & 0xffffu;   // rule 7
+        f.f0 = g.img0 | (j == 4 ? lenw | (idw << 16) : 0u) | (j == 5 ? foffw : 0u) | (j == 6 ? csum : 0u);
+        if constexpr (TSO) {
+            f.f1 = g.img1;
+            if (seg_of(g)) {   // tcp_seqno and the flags of segment jf (nstack_tso.h rule 4)
+                const uint32_t T = 14u + g.hlen, sw = __builtin_bswap32(g.seq0 + at);
+                uint32_t fl = g.tfl;
+                if (jf + 1u < g.cnt) fl &= ~(kTcpFin | kTcpPsh);
+                if (jf) fl &= ~kTcpCwr;
+                f.f0 |= tcp_words((uint32_t)j, T, sw, fl, 0u);
+                f.f1 |= tcp_words((uint32_t)j + 16u, T, sw, fl, 0u);
+            }
+        }
         f.F = frame_len(f.I);
         f.m = (f.F + (uint32_t)kSegBytes - 1u) / (uint32_t)kSegBytes;
         f.fo = p.out + (g.slot0 + jf) * p.slot;
@@ -203,14 +284,39 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         const uint32_t e0 = row_get(h0, 0u), e1 = row_get(h0, 1u), e2 = row_get(h0, 2u);
         const uint32_t w0 = __builtin_amdgcn_alignbyte(e1, e0, r);   // vhl, tos, ip_len
         const uint32_t w4 = __builtin_amdgcn_alignbyte(e2, e1, r);   // id, ip_foff
-        One o = plan_fields(D, w0 & 0xffu, swap16(w0 >> 16), swap16(w4 >> 16), p.mtu, p.flags);
+        // the datagram's dwords e and e + 1 of that grid (128 bytes from floor4 on)
+        auto hget = [&](int e) -> uint32_t {
+            const uint32_t v0 = row_get(h0, (uint32_t)e & 15u), v1 = row_get(h1, (uint32_t)e & 15u);
+            return e < 0 ? 0u : (e < 16 ? v0 : v1);
+        };
+        One o;
         g.slot0 = p.first[i];
-        if (o.cnt && (g.slot0 > p.slots || o.cnt > p.slots - g.slot0)) {   // rule 9
-            o.status |= kNoRoom;
-            o.cnt = 0u;
-        }
         uint32_t l4bits = 0u, fo = 0u;
-        if constexpr (L4) {   // proto; segment length, field offset
+        if constexpr (TSO) {   // nstack_tso.h rules 1-3 and 6 (tso_plan.hpp); the rest as below
+            const uint32_t w8 = __builtin_amdgcn_alignbyte(row_get(h0, 3u), e2, r);   // ttl, proto, checksum
+            g.proto = (w8 >> 8) & 0xffu;
+            const uint32_t b = (w0 & 0x0fu) * 4u + 12u + r;   // segment bytes 12, 13: looked at for candidates only
+            const uint32_t tw = __builtin_amdgcn_alignbyte(hget((int)(b >> 2) + 1), hget((int)(b >> 2)), b & 3u);
+            uint32_t mss = 0u;
+            if (p.mss != nullptr) mss = p.mss[(p.flags & kFlagMssOne) ? 0ull : i];
+            const TsoOne t = tso_fields(D, w0 & 0xffu, swap16(w0 >> 16), swap16(w4 >> 16), g.proto, tw & 0xffu,
+                                        (tw >> 8) & 0xffu, mss, p.mtu, p.flags);
+            o = t.o;
+            fo = t.fo;
+            g.thl = t.thl;
+            if (o.cnt && (g.slot0 > p.slots || o.cnt > p.slots - g.slot0)) {   // rule 9
+                o.status = tso_no_room(o.status);
+                o.cnt = 0u;
+            }
+            l4bits = o.status & kL4CsumSet;
+        } else {
+            o = plan_fields(D, w0 & 0xffu, swap16(w0 >> 16), swap16(w4 >> 16), p.mtu, p.flags);
+            if (o.cnt && (g.slot0 > p.slots || o.cnt > p.slots - g.slot0)) {   // rule 9
+                o.status |= kNoRoom;
+                o.cnt = 0u;
+            }
+        }
+        if constexpr (L4 && !TSO) {   // proto; segment length, field offset
             const uint32_t w8 = __builtin_amdgcn_alignbyte(row_get(h0, 3u), e2, r);   // ttl, proto, checksum
             g.proto = (w8 >> 8) & 0xffu;
             if (!(o.status & (kBadHdr | kBadLen)))
@@ -227,10 +333,6 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         // frame dword d holds frame bytes 4 d .. 4 d + 3 = datagram bytes 4 d - 14 ..: dwords
         // d - 4 + c and the next of the datagram's grid, shifted by (2 + r) & 3
         const uint32_t c = (2u + r) >> 2, sh = (2u + r) & 3u;
-        auto hget = [&](int e) -> uint32_t {
-            const uint32_t v0 = row_get(h0, (uint32_t)e & 15u), v1 = row_get(h1, (uint32_t)e & 15u);
-            return e < 0 ? 0u : (e < 16 ? v0 : v1);
-        };
         const int e = j - 4 + (int)c;
         g.img0 = __builtin_amdgcn_alignbyte(hget(e + 1), hget(e), sh);
         g.img1 = __builtin_amdgcn_alignbyte(hget(e + 17), hget(e + 16), sh);
@@ -240,6 +342,22 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         }
         if (j == 3) g.img0 = (g.img0 & 0xffff0000u) | 0x0008u;          // 08 00
         if (j >= 4 && j <= 6) g.img0 &= 0xffff0000u;                     // ip_len, ip_foff, checksum
+        if constexpr (TSO) {
+            g.hb = o.hlen + g.thl;
+            if (g.thl) {   // what every segment gets its own value of leaves the image
+                const uint32_t T = 14u + o.hlen, ds = (T + 4u) >> 2, df = (T + 13u) >> 2;
+                auto iget = [&](uint32_t d) -> uint32_t {
+                    const uint32_t v0 = row_get(g.img0, d & 15u), v1 = row_get(g.img1, d & 15u);
+                    return d < 16u ? v0 : v1;
+                };
+                g.seq0 = __builtin_bswap32((iget(ds) >> 16) | (iget(ds + 1u) << 16));
+                g.tfl = iget(df) >> 24;
+                g.id0 = swap16(w4 & 0xffffu);
+                if (j == 4) g.img0 = 0u;   // ip_id too
+                g.img0 &= ~tcp_words((uint32_t)j, T, 0xffffffffu, 0xffu, 0xffffu);
+                g.img1 &= ~tcp_words((uint32_t)j + 16u, T, 0xffffffffu, 0xffu, 0xffffu);
+            }
+        }
         const int hend = 14 + (int)o.hlen;
         const uint32_t k0 = keep_range(g.img0, 4 * j, 14, hend), k1 = keep_range(g.img1, 64 + 4 * j, 14, hend);
         g.hsum = fold64(row_sum((k0 & 0xffffu) + (k0 >> 16) + (k1 & 0xffffu) + (k1 >> 16)));
@@ -261,6 +379,14 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                 g.old = (q0 & 2u) ? wd >> 16 : wd & 0xffffu;
                 g.fidx = o.max ? fo / o.max : 0u;
                 g.qf = q0 - g.fidx * o.max;
+                if constexpr (TSO) {
+                    if (g.thl) {   // every frame holds the field, at q0; the frame's length joins per frame
+                        const uint32_t src = __builtin_amdgcn_alignbyte(d7, d6, 2u), dst = __builtin_amdgcn_alignbyte(d8, d7, 2u);
+                        g.ps = 0xffffu + (src & 0xffffu) + (src >> 16) + (dst & 0xffffu) + (dst >> 16) + 0x0600u;
+                        g.fidx = o.cnt - 1u;   // in order
+                        g.qf = q0;
+                    }
+                }
             }
         }
         return g;
@@ -281,7 +407,7 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                     n.act = false;
                     if constexpr (L4) n.pre = false;
                     n.k = 0;
-                    n.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
+                    n.fr = idle_frame<M>();
                     go = false;
                 } else {
                     const Dg g = load_dg(cur++);
@@ -294,7 +420,7 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                             n.t = 0;
                             n.jf = frag_at(g, 0u);
                             n.fr = frame_of(g, n.jf);
-                            n.pre = g.cnt == 1u && g.qf != 0u && n.fr.m > 1u;
+                            n.pre = (g.cnt == 1u || seg_of(g)) && g.qf != 0u && n.fr.m > 1u;
                         } else {
                             n.fr = frame_of(g, 0u);
                         }
@@ -322,7 +448,7 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                         } else {
                             n.jf = frag_at(n.g, n.t);
                             n.fr = frame_of(n.g, n.jf);
-                            n.pre = n.t + 1u == n.g.cnt && n.g.qf != 0u && n.fr.m > 1u;
+                            n.pre = (n.t + 1u == n.g.cnt || seg_of(n.g)) && n.g.qf != 0u && n.fr.m > 1u;
                         }
                     }
                 } else {
@@ -382,7 +508,7 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         rxv::align_words(d, ch.r, w);
         // ---- the 14 + hlen bytes in front: from the header image (a first segment shorter than
         //      that leaves the rest of them to the second) ----
-        const int hend = 14 + (int)c.g.hlen;
+        const int hend = 14 + (int)hb_of(c.g);
         if (__any(c.act && rel < hend && rel > -kChunkBytes)) {
 #pragma unroll
             for (int i = 0; i < kChunkWords; i++) {
@@ -392,7 +518,9 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                     const int D0 = q >> 2, D1 = D0 + 1;   // -1 where the word starts in front of the frame: masked below
                     uint32_t lo = row_get(fr.f0, (uint32_t)D0 & 15u), hi = row_get(fr.f0, (uint32_t)D1 & 15u);
                     if (__any(hit && D1 >= 16)) {
-                        const uint32_t lo1 = row_get(c.g.img1, (uint32_t)D0 & 15u), hi1 = row_get(c.g.img1, (uint32_t)D1 & 15u);
+                        uint32_t i1 = c.g.img1;
+                        if constexpr (TSO) i1 = fr.f1;
+                        const uint32_t lo1 = row_get(i1, (uint32_t)D0 & 15u), hi1 = row_get(i1, (uint32_t)D1 & 15u);
                         lo = D0 >= 16 ? lo1 : lo;
                         hi = D1 >= 16 ? hi1 : hi;
                     }
@@ -416,7 +544,8 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         // ---- L4: the sums, and at the datagram's last frame the field ----
         if constexpr (L4) {
             const bool fend = c.act && c.k + 1u == fr.m;
-            const bool fin = c.act && c.t + 1u == c.g.cnt && c.g.qf != 0u;   // the frame that holds the field
+            const bool seg = seg_of(c.g);                                      // TSO: every frame holds its own field
+            const bool fin = c.act && (c.t + 1u == c.g.cnt || seg) && c.g.qf != 0u;   // the frame that holds the field
             const bool again = fin && !c.pre && fr.m > 1u;                    // summed by the visit before
             uint64_t a = 0, b = 0;
             rxv::add_sums(w, rel, 0, 0u, a, b);
@@ -427,12 +556,16 @@ __device__ __forceinline__ void frame_walk(FParams p) {
                 if (fend) dsum += (fr.F & 1u) ? swap16(ft) : ft;   // the end's grid to the start's
                 if (__any(fend && fin && !again)) {
                     const rxv::Sums q = rxv::reduce_sums(dsum, 0ull, 0u, false, false);
-                    const uint64_t x = (uint64_t)c.g.ps + q.tot_s + (uint64_t)c.g.cnt * (0xffffu - c.g.mac) + (0xffffu - c.g.old);
+                    uint64_t x = (uint64_t)c.g.ps + q.tot_s + (uint64_t)c.g.cnt * (0xffffu - c.g.mac) + (0xffffu - c.g.old);
+                    if constexpr (TSO) {   // one frame's sum, the pseudo header with this segment's thl + plen
+                        const uint64_t xs = (uint64_t)c.g.ps + swap16(fr.I - c.g.hlen) + q.tot_s + (0xffffu - c.g.mac);
+                        x = seg ? xs : x;
+                    }
                     uint32_t v = c.g.ps ? ~fold64(x) & 0xffffu : 0u;   // TXD_F_UDP_ZERO: 0, nothing summed
                     if (v == 0u && c.g.ps != 0u && c.g.proto == 17u) v = 0xffffu;   // RFC 768
                     if (fend && fin && !again) dl4 = v ^ c.g.old;
                 }
-                if (fend && !c.pre && c.t + 1u == c.g.cnt) dsum = 0;   // the datagram is done
+                if (fend && ((!c.pre && c.t + 1u == c.g.cnt) || seg)) dsum = 0;   // the datagram (TSO: the frame) is done
             }
             const bool pat = fin && !c.pre;
             if (__any(pat)) xor_field(w, pat ? (int)c.g.qf - rel : rxv::kNoField, dl4);
@@ -495,20 +628,26 @@ __device__ __forceinline__ void frame_walk(FParams p) {
         A.pre = false;
     }
     A.g = Dg{};
-    A.fr = Frame{0, 0, 0u, 0u, 1u, 0u};
+    A.fr = idle_frame<M>();
     advance(A, true);
     rxv::two_in_flight<Chunk>(A, next, issue, process);
 }
 
 template <bool FCSW, int NT>
 __global__ __launch_bounds__(NT, 1) void txf_kernel(FParams p) {
-    frame_walk<FCSW, false, NT>(p);
+    frame_walk<FCSW, Mode::kPlain, NT>(p);
 }
 
 // ip_tx_frame_l4_*: the framer that also fills every datagram's L4 checksum.
 template <bool FCSW, int NT>
 __global__ __launch_bounds__(NT, 1) void txd_kernel(FParams p) {
-    frame_walk<FCSW, true, NT>(p);
+    frame_walk<FCSW, Mode::kL4, NT>(p);
+}
+
+// ip_tx_tso_*: that, with eligible TCP datagrams cut into MSS segments.
+template <bool FCSW, int NT>
+__global__ __launch_bounds__(NT, 1) void tso_kernel(FParams p) {
+    frame_walk<FCSW, Mode::kTso, NT>(p);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -554,6 +693,41 @@ __global__ __launch_bounds__(kPlanThreads) void txf_plan_kernel(FParams p, uint3
     if (threadIdx.x == kPlanThreads - 1) tot[blockIdx.x] = incl;
 }
 
+// The same for include/nstack_tso.h: header bytes 0..9 and, for candidates (tso_plan.hpp), segment
+// bytes 12 and 13; status[i] is the whole word. Every read lies inside the datagram and [lo4, hi4).
+__global__ __launch_bounds__(kPlanThreads) void tso_plan_kernel(FParams p, uint32_t *status, uint64_t *first,
+                                                                uint64_t *tot) {
+    __shared__ uint64_t sh[kPlanThreads];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+    uint64_t cnt = 0;
+    if (i < p.n) {
+        const uint64_t a = p.dg + p.off[i];
+        const uint32_t D = p.len[i];
+        auto word = [&](uint64_t b) -> uint32_t {   // the four bytes from datagram byte b on (inside the datagram)
+            const uint64_t ad = a + b, a4 = ad & ~3ull;
+            uint32_t lo = 0u, hi = 0u;
+            if (a4 >= p.lo4 && a4 + 4 <= p.hi4) lo = fcs::gload<uint32_t>(a4);
+            if ((ad & 3ull) && a4 + 8 <= p.hi4) hi = fcs::gload<uint32_t>(a4 + 4);
+            return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)ad & 3u);
+        };
+        TsoOne t{plan_fields(D, 0u, 0u, 0u, p.mtu, p.flags & kKnownFlags), 0u, 0u};
+        if (D >= 20u) {
+            const uint32_t w0 = word(0), w4 = word(4), w8 = word(8);
+            const uint32_t hlen = (w0 & 0x0fu) * 4u, foff = swap16(w4 >> 16), proto = (w8 >> 8) & 0xffu;
+            uint32_t tw = 0u;
+            if (hlen >= 20u && hlen <= D && tso_candidate(D, hlen, proto, foff)) tw = word(hlen + 12u);
+            uint32_t mss = 0u;
+            if (p.mss != nullptr) mss = p.mss[(p.flags & kFlagMssOne) ? 0ull : i];
+            t = tso_fields(D, w0 & 0xffu, swap16(w0 >> 16), foff, proto, tw & 0xffu, (tw >> 8) & 0xffu, mss, p.mtu, p.flags);
+        }
+        if (status != nullptr) status[i] = t.o.status;
+        first[i] = t.o.cnt;
+        cnt = t.o.cnt;
+    }
+    const uint64_t incl = block_scan_incl(cnt, sh);
+    if (threadIdx.x == kPlanThreads - 1) tot[blockIdx.x] = incl;
+}
+
 // One workgroup: tot[b] becomes the sum of the blocks in front of b; *total the sum of all.
 __global__ __launch_bounds__(kPlanThreads) void txf_scan_totals_kernel(uint64_t *tot, uint64_t nb, uint64_t *total) {
     __shared__ uint64_t sh[kPlanThreads];
@@ -579,40 +753,55 @@ __global__ __launch_bounds__(kPlanThreads) void txf_add_kernel(uint64_t *first, 
 }
 
 namespace {
-std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone};
+std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone}, g_last_route_tso{(int)Route::kNone};
 }
 Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
 Route last_launch_l4() { return (Route)g_last_route_l4.load(std::memory_order_relaxed); }
+Route last_launch_tso() { return (Route)g_last_route_tso.load(std::memory_order_relaxed); }
 
-hipError_t launch_txf(const FParams &p, bool l4, int cus, hipStream_t st) {
+hipError_t launch_txf(const FParams &p, Mode mode, int cus, hipStream_t st) {
     (void)hipGetLastError();   // report this launch's own error, not an earlier call's
     if (!p.n) return hipSuccess;
     if (!p.ctr) return hipErrorInvalidValue;
     const bool fcsw = (p.flags & kFlagFcs) != 0;
-    if (l4) g_last_route_l4.store((int)(fcsw ? Route::kGeneralL4Fcs : Route::kGeneralL4), std::memory_order_relaxed);
+    if (mode == Mode::kTso) g_last_route_tso.store((int)(fcsw ? Route::kTsoFcs : Route::kTso), std::memory_order_relaxed);
+    else if (mode == Mode::kL4) g_last_route_l4.store((int)(fcsw ? Route::kGeneralL4Fcs : Route::kGeneralL4), std::memory_order_relaxed);
     else g_last_route.store((int)(fcsw ? Route::kGeneralFcs : Route::kGeneral), std::memory_order_relaxed);
     // one workgroup per CU, persistent over the datagrams (a quarter-wave per run of datagrams)
     const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
     const int grid = (int)(want < (uint64_t)cus ? want : (uint64_t)cus);
-    if (l4 && fcsw) hipLaunchKernelGGL((txd_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
-    else if (l4) hipLaunchKernelGGL((txd_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    if (mode == Mode::kTso && fcsw) hipLaunchKernelGGL((tso_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else if (mode == Mode::kTso) hipLaunchKernelGGL((tso_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else if (mode == Mode::kL4 && fcsw) hipLaunchKernelGGL((txd_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
+    else if (mode == Mode::kL4) hipLaunchKernelGGL((txd_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
     else if (fcsw) hipLaunchKernelGGL((txf_kernel<true, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
     else hipLaunchKernelGGL((txf_kernel<false, kThreads>), dim3(grid), dim3(kThreads), 0, st, p);
     return hipGetLastError();
 }
 
-hipError_t launch_plan(const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
+namespace {
+template <class K>
+hipError_t launch_plan_with(K count_kernel, const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
     (void)hipGetLastError();
     if (!p.n) return hipSuccess;
     const uint64_t nb = (p.n + kPlanThreads - 1) / kPlanThreads;
     if (nb > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(txf_plan_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p, status, first, tot);
+    hipLaunchKernelGGL(count_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p, status, first, tot);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(txf_scan_totals_kernel, dim3(1), dim3(kPlanThreads), 0, st, tot, nb, first + p.n);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(txf_add_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, first, (const uint64_t *)tot, p.n);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_plan(const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
+    return launch_plan_with(txf_plan_kernel, p, status, first, tot, st);
+}
+
+hipError_t launch_plan_tso(const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
+    return launch_plan_with(tso_plan_kernel, p, status, first, tot, st);
 }
 
 }  // namespace txf
