@@ -38,7 +38,9 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "tx_frame_l4_dev", "tx_frame_l4_host", "txd_last_launch", "TXD_EXPORTS", "TXD_F_UDP_ZERO", "TXD_L4_CSUM_SET",
            "TXD_L4_SHORT", "TXD_PROTO_SHIFT",
            "tx_tso_count", "tx_tso_plan_dev", "tx_tso_dev", "tx_tso_host", "tso_last_launch", "TSO_EXPORTS",
-           "TSO_F_ID_FIXED", "TSO_F_MSS_ONE", "TSO_SEGMENTED"]
+           "TSO_F_ID_FIXED", "TSO_F_MSS_ONE", "TSO_SEGMENTED",
+           "rx_gro_plan_host", "rx_gro_plan_dev", "rx_gro_dev", "rx_gro_host", "gro_last_launch", "GRO_EXPORTS",
+           "GRO_CAND", "GRO_MERGED", "GRO_FIN", "GRO_PSH", "GROD_MERGED"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -112,6 +114,11 @@ TXD_PROTO_SHIFT = 16
 TSO_EXPORTS = ["ip_tx_tso_count", "ip_tx_tso_plan_dev", "ip_tx_tso_dev", "ip_tx_tso_host", "fcs_debug_tso_last_launch"]
 TSO_F_ID_FIXED, TSO_F_MSS_ONE = 0x200, 0x400
 TSO_SEGMENTED = 0x400
+
+# include/nstack_gro.h — one-pass RX coalescing (its own list, as TSO_EXPORTS)
+GRO_EXPORTS = ["ip_rx_gro_plan_host", "ip_rx_gro_plan_dev", "ip_rx_gro_dev", "ip_rx_gro_host", "fcs_debug_gro_last_launch"]
+GRO_CAND, GRO_MERGED, GRO_FIN, GRO_PSH = 0x1000, 0x2000, 0x4000, 0x8000
+GROD_MERGED = 0x400
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -277,6 +284,11 @@ def _bind(path: str) -> ctypes.CDLL:
         "ip_rx_reasm_l4_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, vp]),
         "ip_rx_reasm_l4_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, vp, vp]),
         "fcs_debug_rxd_last_launch": (i32, [c.c_char_p, u64]),
+        "ip_rx_gro_plan_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "ip_rx_gro_plan_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ip_rx_gro_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, vp]),
+        "ip_rx_gro_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, vp, vp]),
+        "fcs_debug_gro_last_launch": (i32, [c.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1011,3 +1023,55 @@ def rxr_last_host_chunks() -> list:
     buf = (ctypes.c_uint64 * max(k, 1))()
     load().fcs_debug_rxr_last_host_chunks(buf, k)
     return list(buf[:k])
+
+
+# ---- one-pass RX coalescing (include/nstack_gro.h) ----
+def rx_gro_plan_host(arena, arena_bytes: int, off, length, n: int, fstat, dst, dgi, doff, dlen, dlead=None,
+                     flags: int = 0, verdict=None, drop_mask: int = 0, align: int = 1) -> int:
+    """rx_reasm_plan_host with runs of in-order TCP segments planned as one merged datagram each
+    (GRO_CAND, GRO_MERGED, GRO_FIN, GRO_PSH in fstat). Host arithmetic, no GPU. Returns m."""
+    return _check(load().ip_rx_gro_plan_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                             _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"),
+                                             _ptr(fstat), _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(dlead)),
+                  "ip_rx_gro_plan_host")
+
+
+def rx_gro_plan_dev(arena, arena_bytes: int, off, length, n: int, fstat, dst, dgi, doff, dlen, dlead=None, counts=None,
+                    flags: int = 0, verdict=None, drop_mask: int = 0, align: int = 1, stream=None) -> None:
+    """The same arrays in device memory, plus counts[2] = {m, bytes} (u64); asynchronous on `stream`."""
+    _check(load().ip_rx_gro_plan_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                     _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"), _ptr(fstat),
+                                     _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(dlead), _ptr(counts),
+                                     _stream(stream)),
+           "ip_rx_gro_plan_dev")
+
+
+def rx_gro_dev(arena, arena_bytes: int, off, length, n: int, pstat, dst, dgi, doff, dlen, counts, out, out_bytes: int,
+               dverdict, flags: int = 0, fstat=None, bad_mask: int = 0, bad=None, stream=None) -> None:
+    """rx_reasm_l4_dev on the arrays of rx_gro_plan_dev: merged datagrams are built with a fresh TCP
+    checksum and get GROD_MERGED | 6 << RXD_PROTO_SHIFT. Device arrays; asynchronous on `stream`."""
+    _check(load().ip_rx_gro_dev(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"), _ptr(pstat),
+                                _ptr(dst), _ptr(dgi), _ptr(doff), _ptr(dlen), _ptr(counts), _ptr(out), out_bytes,
+                                _ptr(fstat), _u32(bad_mask, "bad_mask"), _ptr(dverdict), _ptr(bad), _stream(stream)),
+           "ip_rx_gro_dev")
+
+
+def rx_gro_host(arena, arena_bytes: int, off, length, n: int, out, out_bytes: int, dverdict, flags: int = 0,
+                verdict=None, drop_mask: int = 0, align: int = 1, fstat=None, doff=None, dlen=None, dlead=None,
+                bad_mask: int = 0) -> tuple:
+    """Host form: rx_reasm_l4_host with coalescing. Returns (m, the number of datagrams with
+    dverdict & bad_mask); rxr_last_host_chunks() reports its chunks."""
+    bad = ctypes.c_uint64(0)
+    m = _check(load().ip_rx_gro_host(_ptr(arena), arena_bytes, _ptr(off), _ptr(length), n, _u32(flags, "flags"),
+                                     _ptr(verdict), _u32(drop_mask, "drop_mask"), _u32(align, "align"), _ptr(out),
+                                     out_bytes, _ptr(fstat), _ptr(doff), _ptr(dlen), _ptr(dlead),
+                                     _u32(bad_mask, "bad_mask"), _ptr(dverdict), ctypes.addressof(bad)),
+               "ip_rx_gro_host")
+    return m, int(bad.value)
+
+
+def gro_last_launch() -> str:
+    """The kernel the last coalescing build launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_gro_last_launch(buf, 32), "fcs_debug_gro_last_launch")
+    return buf.value.decode()

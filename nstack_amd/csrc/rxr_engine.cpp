@@ -1,4 +1,5 @@
-// rxr_engine.cpp — the C ABI of include/nstack_rxr.h and include/nstack_rxd.h around rxr_kernel.hip.
+// rxr_engine.cpp — the C ABI of include/nstack_rxr.h, include/nstack_rxd.h and include/nstack_gro.h
+// around rxr_kernel.hip and gro_kernel.hip.
 //
 // Device forms validate and launch; the device plan takes its scratch from hipMallocAsync on the
 // caller's stream. The host form plans on the host (rxr_plan.hpp), checks every frame and the
@@ -10,17 +11,20 @@
 // delivered datagram never travel. No CPU path: a failure is returned, never answered on the host,
 // and the FCS engine's host-batch and fallback counters are not touched. The forms of nstack_rxd.h are
 // the same calls with the summing build and the verdict launch behind it (an L4 request: null for the
-// plain forms); the host form brings a chunk's verdict words back with its datagrams.
+// plain forms); the host form brings a chunk's verdict words back with its datagrams. The forms of
+// nstack_gro.h are those of nstack_rxd.h with the coalescing plan, build and finishing launch.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
 #include <cstring>
 #include <vector>
 
+#include "../../include/nstack_gro.h"
 #include "../../include/nstack_rxd.h"
 #include "../../include/nstack_rxr.h"
 #include "fcs_device.hpp"
 #include "fcs_error.hpp"
+#include "gro_launch.hpp"
 #include "host_pipe.hpp"
 #include "rxr_launch.hpp"
 
@@ -68,9 +72,12 @@ constexpr uint64_t kOutBytes = 32ull << 20;    // a chunk's datagrams with their
 constexpr uint64_t kChunkDgs = 1ull << 16;
 constexpr uint64_t kChunkFrames = 1ull << 18;
 constexpr int kDepth = 2;
-// One datagram always fits a chunk: it is at most 65535 bytes (+ 127 of gap) in at most 8190 frames
-// of at most 14 + 60 + 65515 gathered bytes each whose payloads add up to at most 65515 bytes.
+// One datagram always fits a chunk: it is at most 65535 bytes (+ 127 of gap), reassembled from at
+// most 8190 frames of 14 + 60 gathered header bytes each whose payloads add up to at most 65515
+// bytes, or merged (nstack_gro.h) from at most 32768 members of 14 + 60 + 60 gathered header bytes
+// each whose payloads add up to less than 65535 bytes.
 static_assert(8190ull * 74 + 65535 <= kInBytes && 65535 + 127 <= kOutBytes && 8190 <= kChunkFrames, "a datagram fits a chunk");
+static_assert(gro::kMaxMembers * 134ull + 65535 <= kInBytes && gro::kMaxMembers <= kChunkFrames, "a merged datagram fits a chunk");
 
 struct RxrPipe;   // names this engine's pipelines (host_pipe.hpp)
 thread_local std::vector<uint64_t> t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
@@ -88,7 +95,8 @@ struct HostPlan {
 };
 
 // dverdict: null for the plain form; else the caller's verdict words (nstack_rxd.h), one per datagram.
-int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, uint8_t *out, uint32_t *dverdict) {
+// gro: the coalescing build and finishing launch (nstack_gro.h; hp is then gro::plan_batch's).
+int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, uint8_t *out, uint32_t *dverdict, bool gro) {
     int dev = 0, cus = 0;
     int rc = fcs::engine_device0(&dev, &cus);
     if (rc) return rc;
@@ -152,6 +160,7 @@ int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, 
             p.counts = s.d<uint64_t>(kCnt);
             p.dverdict = s.d<uint32_t>(kVerd);
             p.bad_mask = 0;   // bad is counted on the host
+            p.gro = gro ? 1u : 0u;
         }
         if ((rc = launch(p, dev, cus, st))) return rc;
         HIPTRY(hipMemcpyAsync(s.h<void>(kOut), s.d<void>(kOut), ob, hipMemcpyDeviceToHost, st), "D2H datagrams");
@@ -171,8 +180,9 @@ int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, 
     return rc ? (int64_t)rc : (int64_t)m;
 }
 
-// The device build of both headers. l4: the form of nstack_rxd.h, which needs counts and dverdict.
-int build_dev(bool l4, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+// The device build of the three headers. l4: the form of nstack_rxd.h, which needs counts and
+// dverdict; gro (with l4): that of nstack_gro.h.
+int build_dev(bool l4, bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
               uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi, const uint64_t *doff,
               const uint32_t *dlen, const uint64_t *counts, void *out, uint64_t out_bytes, uint32_t *fstat,
               uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad, void *stream) {
@@ -209,6 +219,7 @@ int build_dev(bool l4, const void *arena, uint64_t arena_bytes, const uint64_t *
         p.dverdict = dverdict;
         p.bad = (unsigned long long *)bad;
         p.bad_mask = bad_mask;
+        p.gro = gro ? 1u : 0u;
     }
     return launch(p, dev, cus, st);
 }
@@ -234,10 +245,14 @@ int64_t ether_rx_reasm_plan_host(const void *arena, uint64_t arena_bytes, const 
     return m;
 }
 
-int ether_rx_reasm_plan_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
-                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
-                            uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen,
-                            uint32_t *dlead, uint64_t *counts, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// The device plan of nstack_rxr.h, or with gro that of nstack_gro.h.
+int plan_dev(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+             uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat, uint64_t *dst,
+             uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint64_t *counts, void *stream) {
     int rc = check_call(flags, align, n);
     if (rc) return rc;
     if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen)))
@@ -268,20 +283,39 @@ int ether_rx_reasm_plan_dev(const void *arena, uint64_t arena_bytes, const uint6
     p.counts = counts;
     // scratch that lives on the stream, between the launches
     void *mem = nullptr;
-    HIPTRY(hipMallocAsync(&mem, rxr::scratch_bytes(n), st), "hipMallocAsync(plan scratch)");
+    const uint64_t rb = (rxr::scratch_bytes(n) + 15) & ~15ull;   // the coalescing plan's scratch lies behind
+    HIPTRY(hipMallocAsync(&mem, gro ? rb + gro::scratch_bytes(n) : rxr::scratch_bytes(n), st), "hipMallocAsync(plan scratch)");
     hipError_t e = hipMemsetAsync(mem, 0, rxr::zeroed_bytes(n), st);
-    if (e == hipSuccess) e = rxr::launch_plan(p, rxr::carve(mem, n), st);
+    if (gro) {
+        void *gmem = (uint8_t *)mem + rb;
+        if (e == hipSuccess) e = hipMemsetAsync(gmem, 0, gro::zeroed_bytes(n), st);
+        if (e == hipSuccess) e = gro::launch_plan(p, rxr::carve(mem, n), gro::carve(gmem, n), st);
+    } else if (e == hipSuccess) {
+        e = rxr::launch_plan(p, rxr::carve(mem, n), st);
+    }
     const hipError_t e2 = hipFreeAsync(mem, st);
-    HIPTRY(e, "launching the rxr plan kernels");
+    HIPTRY(e, "launching the plan kernels");
     HIPTRY(e2, "hipFreeAsync(plan scratch)");
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ether_rx_reasm_plan_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
+                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
+                            uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen,
+                            uint32_t *dlead, uint64_t *counts, void *stream) {
+    return plan_dev(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead,
+                    counts, stream);
 }
 
 int ether_rx_reasm_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
                        uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
                        const uint64_t *doff, const uint32_t *dlen, void *out, uint64_t out_bytes, uint32_t *fstat,
                        void *stream) {
-    return build_dev(false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, nullptr, out, out_bytes, fstat,
+    return build_dev(false, false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, nullptr, out, out_bytes, fstat,
                      0u, nullptr, nullptr, stream);
 }
 
@@ -289,8 +323,21 @@ int ether_rx_reasm_dev(const void *arena, uint64_t arena_bytes, const uint64_t *
 
 namespace {
 
-// The host form of both headers: dverdict is null for ether_rx_reasm_host.
-int64_t reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+// The host arithmetic of a plan call: rxr::plan_batch, or with gro gro::plan_batch.
+int64_t plan_host(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                  uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat, uint64_t *dst,
+                  uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead) {
+    uint64_t bad = 0;
+    const int64_t m = (gro ? gro::plan_batch : rxr::plan_batch)((const uint8_t *)arena, arena_bytes, off, len, n, flags, verdict,
+                                                                drop_mask, align, fstat, dst, dgi, doff, dlen, dlead, &bad);
+    if (m < 0)
+        return fcs::set_error(EINVAL, "frame %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
+                              (unsigned long long)off[bad], len[bad], (unsigned long long)arena_bytes);
+    return m;
+}
+
+// The host form of the three headers: dverdict is null for ether_rx_reasm_host; gro: nstack_gro.h.
+int64_t reasm_host(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
                    uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, void *out,
                    uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen, uint32_t *dlead,
                    uint32_t *dverdict) {
@@ -309,13 +356,9 @@ int64_t reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off,
     hp.dlead.resize(n);
     hp.dst.resize(n);
     hp.doff.resize(n + 1);
-    uint64_t bad = 0;
-    const int64_t m = rxr::plan_batch((const uint8_t *)arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align,
-                                      hp.fstat.data(), hp.dst.data(), hp.dgi.data(), hp.doff.data(), hp.dlen.data(),
-                                      hp.dlead.data(), &bad);
-    if (m < 0)
-        return fcs::set_error(EINVAL, "frame %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
-                              (unsigned long long)off[bad], len[bad], (unsigned long long)arena_bytes);
+    const int64_t m = plan_host(gro, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, hp.fstat.data(),
+                                hp.dst.data(), hp.dgi.data(), hp.doff.data(), hp.dlen.data(), hp.dlead.data());
+    if (m < 0) return m;
     hp.m = (uint64_t)m;
     const uint64_t need = hp.m ? hp.doff[hp.m - 1] + hp.dlen[hp.m - 1] : 0;   // rule 8: the last datagram's end
     if (need > out_bytes)
@@ -340,7 +383,7 @@ int64_t reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off,
     int dev = 0, cus = 0;   // no CPU path, also for a batch that delivers nothing
     if ((rc = fcs::engine_device0(&dev, &cus))) return rc;
     int64_t r = (int64_t)hp.m;
-    if (hp.m) r = run_host((const uint8_t *)arena, off, hp, (uint8_t *)out, dverdict);
+    if (hp.m) r = run_host((const uint8_t *)arena, off, hp, (uint8_t *)out, dverdict, gro);
     if (r < 0) return r;
     for (uint64_t i = 0; i < n && fstat; i++)
         fstat[i] = hp.fstat[i] | (hp.dgi[i] != rxr::kNone32 ? rxr::kDelivered : 0u);
@@ -358,8 +401,8 @@ int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint6
                             uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
                             void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
                             uint32_t *dlead) {
-    return reasm_host(arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff, dlen,
-                      dlead, nullptr);
+    return reasm_host(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff,
+                      dlen, dlead, nullptr);
 }
 
 // ---- include/nstack_rxd.h ----
@@ -367,7 +410,7 @@ int ip_rx_reasm_l4_dev(const void *arena, uint64_t arena_bytes, const uint64_t *
                        uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
                        const uint64_t *doff, const uint32_t *dlen, const uint64_t *counts, void *out, uint64_t out_bytes,
                        uint32_t *fstat, uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad, void *stream) {
-    return build_dev(true, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, counts, out, out_bytes, fstat,
+    return build_dev(true, false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, counts, out, out_bytes, fstat,
                      bad_mask, dverdict, bad, stream);
 }
 
@@ -376,12 +419,56 @@ int64_t ip_rx_reasm_l4_host(const void *arena, uint64_t arena_bytes, const uint6
                             void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
                             uint32_t *dlead, uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad) {
     if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
-    const int64_t m = reasm_host(arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff,
-                                 dlen, dlead, dverdict);
+    const int64_t m = reasm_host(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat,
+                                 doff, dlen, dlead, dverdict);
     if (m < 0 || !bad) return m;
     *bad = 0;   // counted on the host
     for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
     return m;
+}
+
+// ---- include/nstack_gro.h ----
+int64_t ip_rx_gro_plan_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                            uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat,
+                            uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead) {
+    int rc = check_call(flags, align, n);
+    if (rc) return rc;
+    if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen))) return fcs::set_error(EINVAL, "null pointer");
+    return plan_host(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead);
+}
+
+int ip_rx_gro_plan_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                       uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat,
+                       uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint64_t *counts,
+                       void *stream) {
+    return plan_dev(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead,
+                    counts, stream);
+}
+
+int ip_rx_gro_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n, uint32_t flags,
+                  const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi, const uint64_t *doff, const uint32_t *dlen,
+                  const uint64_t *counts, void *out, uint64_t out_bytes, uint32_t *fstat, uint32_t bad_mask,
+                  uint32_t *dverdict, uint64_t *bad, void *stream) {
+    return build_dev(true, true, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, counts, out, out_bytes, fstat,
+                     bad_mask, dverdict, bad, stream);
+}
+
+int64_t ip_rx_gro_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                       uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, void *out,
+                       uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint32_t bad_mask,
+                       uint32_t *dverdict, uint64_t *bad) {
+    if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
+    const int64_t m = reasm_host(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat,
+                                 doff, dlen, dlead, dverdict);
+    if (m < 0 || !bad) return m;
+    *bad = 0;   // counted on the host
+    for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
+    return m;
+}
+
+// The kernel the last coalescing build launch of this process launched.
+int fcs_debug_gro_last_launch(char *out, uint64_t cap) {
+    return copy_name(rxr::last_launch_gro() == rxr::Route::kGro ? "gro" : "none", out, cap);
 }
 
 // The kernel the last build launch with sums of this process launched.

@@ -24,10 +24,14 @@
 //
 //   * rxr_kernel<NT, true> is the same copy for include/nstack_rxd.h: it also sums what it stores, per
 //     datagram; rxd_verdict_kernel (behind the plan kernels) turns the sums into L4 verdicts.
+//   * rxr_kernel<NT, true, true> is that copy for include/nstack_gro.h: members of a merged TCP
+//     datagram behind the first skip both headers, the first patches its own, and
+//     rxd_verdict_kernel<true> stores the merged datagram's TCP checksum from the sums.
 //
 // The plan kernels follow below: classify, insert, link, decide with the block totals, the scan of
 // the totals in one workgroup, place, finish. One frame per thread; no workgroup waits for another;
-// data passes between the phases only across kernel boundaries.
+// data passes between the phases only across kernel boundaries. The launchers come in three pieces
+// (front, decide, back) so that the coalescing plan (gro_kernel.hip) can put its launches between them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,6 +39,7 @@
 
 #include "fcs_crc.hpp"
 #include "ones_fold.hpp"
+#include "gro_launch.hpp"
 #include "rxr_launch.hpp"
 
 namespace rxr {
@@ -54,20 +59,27 @@ __device__ __forceinline__ void gstore(uint64_t addr, T v) {
     *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
 }
 
-// Rule 7's three fields: the byte at datagram position pos of a head fragment.
-__device__ __forceinline__ uint32_t patch_byte(uint32_t v, uint32_t pos, uint32_t lenw, uint32_t csum) {
+constexpr uint32_t kNoFlagPos = 0xffffffffu;
+
+// Rule 7's three fields: the byte at datagram position pos of a head fragment. With fpos (the first
+// member of a merged datagram, include/nstack_gro.h rule 4): ip_foff is kept, and the TCP flags byte
+// at fpos gets the bits forb.
+__device__ __forceinline__ uint32_t patch_byte(uint32_t v, uint32_t pos, uint32_t lenw, uint32_t csum,
+                                               uint32_t fpos = kNoFlagPos, uint32_t forb = 0u) {
     if (pos == 2u) return lenw & 0xffu;
     if (pos == 3u) return lenw >> 8;
-    if (pos == 6u || pos == 7u) return 0u;
+    if (pos == 6u || pos == 7u) return fpos == kNoFlagPos ? 0u : v;
     if (pos == 10u) return csum & 0xffu;
     if (pos == 11u) return csum >> 8;
+    if (pos == fpos) return v | forb;
     return v;
 }
 
-__device__ __forceinline__ uint32_t patch_word(uint32_t w, uint32_t p0, uint32_t lenw, uint32_t csum) {
+__device__ __forceinline__ uint32_t patch_word(uint32_t w, uint32_t p0, uint32_t lenw, uint32_t csum,
+                                               uint32_t fpos = kNoFlagPos, uint32_t forb = 0u) {
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-        const uint32_t nv = patch_byte((w >> (8 * b)) & 0xffu, p0 + (uint32_t)b, lenw, csum);
+        const uint32_t nv = patch_byte((w >> (8 * b)) & 0xffu, p0 + (uint32_t)b, lenw, csum, fpos, forb);
         w = (w & ~(0xffu << (8 * b))) | (nv << (8 * b));
     }
     return w;
@@ -79,8 +91,13 @@ __device__ __forceinline__ uint32_t grid_byte(uint64_t a, uint32_t v) { return (
 // SUM: the build of include/nstack_rxd.h. Every byte a frame stores is also added to a per-lane
 // one's-complement sum on the destination memory's 16-bit grid (the patched header fields as stored);
 // the row's folded sum goes to the datagram's accumulator p.dverdict[k] with one atomic add per frame.
-template <int NT, bool SUM>
+// GRO (with SUM): the build of include/nstack_gro.h. A member of a merged datagram that is not its
+// first skips its hlen + thl header bytes; the first patches ip_len, the header checksum and the TCP
+// flags byte (rule 4; the TCP checksum is the finishing launch's) and marks its datagram's
+// accumulator with bit 31.
+template <int NT, bool SUM, bool GRO = false>
 __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
+    static_assert(SUM || !GRO, "the coalescing build sums");
     const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
     const uint32_t T = trailer_of(p.flags);
     const uint64_t arena_bytes = p.arena_bytes;
@@ -121,7 +138,17 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                 ok = hlen >= 20u && hlen <= I && I <= F - 14u - T;
             }
             const bool head = (st & kWhole) || (st & kHead);
-            const uint32_t skip = head ? 0u : hlen, nb = I - skip;
+            const bool member = GRO && (st & kWhole) && (st & gro::kMerged), first = member && (st & kHead);
+            uint32_t skip = head ? 0u : hlen;
+            if (GRO && member && ok) {   // the TCP header lies inside the datagram before a byte of it is read
+                ok = hlen + 20u <= I;
+                if (ok && !first) {
+                    const uint32_t thl = ((uint32_t)gload<uint8_t>(start + 14u + hlen + 12u) >> 4) * 4u;
+                    ok = thl >= 20u && hlen + thl <= I;
+                    skip = hlen + thl;
+                }
+            }
+            const uint32_t nb = I - skip;
             ok = ok && has_room(base, D, p.out_bytes) &&                                  // rule 8: the datagram has room
                  d >= base && d - base <= D && nb <= D - (uint32_t)(d - base);           // and the range lies inside it
             if (!ok) {
@@ -129,7 +156,8 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
             } else {
                 fin |= kDelivered;
                 const uint64_t s0 = start + 14u + skip, dA = p.out + d;
-                const bool patch = (st & kFrag) && (st & kHead);
+                const bool patch = ((st & kFrag) && (st & kHead)) || first;
+                const uint32_t fpos = first ? hlen + 13u : kNoFlagPos, forb = first ? gro::flag_bits(st) : 0u;
                 uint32_t lenw = 0u, csum = 0u;
                 uint32_t acc = 0u;   // SUM: at most 256 lines of eight halves and two bytes per lane, below 2^28
                 if (patch) {   // rule 7: the header sum without ip_len, ip_foff and the checksum
@@ -139,7 +167,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                         const uint32_t r = (uint32_t)a & 3u;
                         const uint32_t lo = gload<uint32_t>(a4), hi = r ? gload<uint32_t>(a4 + 4) : 0u;
                         w = __builtin_amdgcn_alignbyte(hi, lo, r);
-                        if (j < 3) w &= 0x0000ffffu;
+                        if (j < 3 && !(first && j == 1)) w &= 0x0000ffffu;   // a merged datagram keeps ip_foff
                     }
                     lenw = swap16(D);
                     const uint32_t sum = row_sum((w & 0xffffu) + (w >> 16));
@@ -150,7 +178,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                 nh = nh < nb ? nh : nb;
                 if ((uint32_t)j < nh) {
                     uint32_t v = gload<uint8_t>(s0 + (uint32_t)j);
-                    if (patch) v = patch_byte(v, (uint32_t)j, lenw, csum);
+                    if (patch) v = patch_byte(v, (uint32_t)j, lenw, csum, fpos, forb);
                     gstore<uint8_t>(dA + (uint32_t)j, (uint8_t)v);
                     if (SUM) acc += grid_byte(dA + (uint32_t)j, v);
                 }
@@ -182,11 +210,11 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                             y.z = __builtin_amdgcn_alignbyte(x[q].w, x[q].z, r);
                             y.w = __builtin_amdgcn_alignbyte(x4[q], x[q].w, r);
                             const uint32_t pos = nh + 16u * b;
-                            if (patch && pos < 12u) {
-                                y.x = patch_word(y.x, pos, lenw, csum);
-                                y.y = patch_word(y.y, pos + 4u, lenw, csum);
-                                y.z = patch_word(y.z, pos + 8u, lenw, csum);
-                                y.w = patch_word(y.w, pos + 12u, lenw, csum);
+                            if (patch && (pos < 12u || (first && pos <= fpos))) {
+                                y.x = patch_word(y.x, pos, lenw, csum, fpos, forb);
+                                y.y = patch_word(y.y, pos + 4u, lenw, csum, fpos, forb);
+                                y.z = patch_word(y.z, pos + 8u, lenw, csum, fpos, forb);
+                                y.w = patch_word(y.w, pos + 12u, lenw, csum, fpos, forb);
                             }
                             gstore<u32x4a4>(db + 16ull * b, y);
                             if (SUM)   // db is 16-byte aligned: eight halves of the memory grid
@@ -199,7 +227,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                 const uint32_t pt = nh + 16u * nblk + (uint32_t)j;
                 if (pt < nb) {
                     uint32_t v = gload<uint8_t>(s0 + pt);
-                    if (patch) v = patch_byte(v, pt, lenw, csum);
+                    if (patch) v = patch_byte(v, pt, lenw, csum, fpos, forb);
                     gstore<uint8_t>(dA + pt, (uint8_t)v);
                     if (SUM) acc += grid_byte(dA + pt, v);
                 }
@@ -209,7 +237,11 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
                     // No overflow of the u32 accumulator: a delivered datagram has at most 8192 frames
                     // (distinct fragment offsets, multiples of 8 below 65536) of at most 0xffff each, and
                     // starts at 0: the total stays below 2^29. Integer adds commute: no order dependence.
-                    if (j == 0 && part) atomicAdd(p.dverdict + k, part);
+                    // GRO: at most 32768 members (distinct seq values of one 32 KiB window) of at most
+                    // 0xffff each stay below 2^31; bit 31 is the first member's mark "merged" for the
+                    // finishing launch, which has no other way to tell.
+                    const uint32_t mark = first ? 0x80000000u : 0u;
+                    if (j == 0 && (part | mark)) atomicAdd(p.dverdict + k, part + mark);
                 }
             }
         }
@@ -363,7 +395,11 @@ __device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *sh, ui
 
 // 4. Each head decides (rule 6). dgi[i] = 1 on the head frame of a delivered datagram, dst[i] its
 // padded length; the blocks' totals of both.
-__global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scratch s) {
+// GRO (include/nstack_gro.h rule 5): a candidate of a coalescible group is a head frame only when it
+// is the group's first member, and then with the merged length; every member reads the same settled
+// accumulator, so all of them decide alike.
+template <bool GRO>
+__global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scratch s, gro::GScratch g) {
     __shared__ uint64_t sh[kPlanThreads];
     const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
     uint32_t D = 0u, is = 0u;
@@ -373,6 +409,14 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scr
         if (st & kWhole) {
             D = me.w3 >> 16;
             is = 1u;
+            if (GRO && (st & gro::kCand)) {
+                const gro::GRec gr = g.rec[i];
+                const gro::GAcc ga = g.acc[gr.group < p.n ? gr.group : i];   // (every candidate has a group)
+                if (gr.group < p.n && gro::coalescible(ga)) {
+                    if (gr.first == (uint32_t)i) D = (((gr.w4 >> 16) & 0x0fu) + ((gr.w4 >> 20) & 0x0fu)) * 4u + (uint32_t)ga.sumP;
+                    else is = 0u, D = 0u;
+                }
+            }
         } else if ((st & kHead) && groupable(st) && s.headof[i] == (uint32_t)i) {
             Acc *a = s.acc + i;
             const bool complete = a->fault == 0u && a->lasts == 1u && a->sumL == (unsigned long long)a->total;
@@ -492,6 +536,12 @@ __device__ __forceinline__ uint32_t load_le32(uint64_t a) {   // any alignment
            ((uint32_t)gload<uint8_t>(a + 3) << 24);
 }
 
+// GRO: the finishing launch of include/nstack_gro.h. Bit 31 of the accumulator is the build's mark
+// "merged" (its first member was delivered). Such a datagram gets its TCP checksum here: everything
+// stored, minus the IP header and the checksum field as the first member brought it, plus the pseudo
+// header; the two bytes lie inside the datagram's own range, and the build is complete (kernel
+// boundary). Every other datagram is judged as without GRO.
+template <bool GRO>
 __global__ __launch_bounds__(kPlanThreads) void rxd_verdict_kernel(RParams p) {
     __shared__ unsigned int wg_bad;
     if (threadIdx.x == 0) wg_bad = 0u;
@@ -510,17 +560,31 @@ __global__ __launch_bounds__(kPlanThreads) void rxd_verdict_kernel(RParams p) {
             const uint32_t hlen = ((uint32_t)gload<uint8_t>(a) & 0x0fu) * 4u;
             if (hlen >= 20u && hlen <= D) {
                 const uint32_t proto = gload<uint8_t>(a + 9), L = D - hlen;
+                const uint32_t stored = GRO ? p.dverdict[k] & 0x7fffffffu : p.dverdict[k];
                 v = proto << kDgProtoShift;
+                if (GRO && (p.dverdict[k] >> 31) && L >= 20u) {
+                    const uint64_t c = a + hlen + 16u;
+                    const uint32_t old = grid_sum(a, hlen) + grid_byte(c, gload<uint8_t>(c)) + grid_byte(c + 1, gload<uint8_t>(c + 1));
+                    const uint32_t mem = fold64((uint64_t)fold64(stored) + (0xffffu - fold64(old)));
+                    const uint32_t seg = ((a + hlen) & 1ull) ? swap16(mem) : mem;
+                    uint32_t none = 0u;
+                    const uint32_t ps = ones::l4_start(6u, load_le32(a + 12), load_le32(a + 16), L, 0u, 0u, none);
+                    const uint32_t field = ~fold64((uint64_t)ps + seg) & 0xffffu;   // as nstack_txs.h rule 6 stores it
+                    gstore<uint8_t>(c, (uint8_t)(field & 0xffu));
+                    gstore<uint8_t>(c + 1, (uint8_t)(field >> 8));
+                    v = gro::kDgMerged | (6u << kDgProtoShift);
+                } else {
                 const uint32_t ufield = (proto == 17u && L >= 8u)
                                             ? (uint32_t)gload<uint8_t>(a + hlen + 6) | ((uint32_t)gload<uint8_t>(a + hlen + 7) << 8)
                                             : 0u;
                 const uint32_t ps = ones::l4_start(proto, load_le32(a + 12), load_le32(a + 16), L, ufield, kDgL4Short, v);
                 if (ps) {
                     // everything stored minus the header, on the memory grid; then on the segment's own
-                    const uint32_t mem = fold64((uint64_t)fold64(p.dverdict[k]) + (0xffffu - fold64(grid_sum(a, hlen))));
+                    const uint32_t mem = fold64((uint64_t)fold64(stored) + (0xffffu - fold64(grid_sum(a, hlen))));
                     const uint32_t seg = ((a + hlen) & 1ull) ? swap16(mem) : mem;
                     v |= kDgL4Checked;
                     if (fold64((uint64_t)ps + seg) != 0xffffu) v |= kDgL4BadCsum;
+                }
                 }
             }
         }
@@ -535,20 +599,24 @@ __global__ __launch_bounds__(kPlanThreads) void rxd_verdict_kernel(RParams p) {
 }
 
 namespace {
-std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone};
+std::atomic<int> g_last_route{(int)Route::kNone}, g_last_route_l4{(int)Route::kNone}, g_last_route_gro{(int)Route::kNone};
 }
 Route last_launch() { return (Route)g_last_route.load(std::memory_order_relaxed); }
 Route last_launch_l4() { return (Route)g_last_route_l4.load(std::memory_order_relaxed); }
+Route last_launch_gro() { return (Route)g_last_route_gro.load(std::memory_order_relaxed); }
 
 hipError_t launch_build(const RParams &p, int cus, hipStream_t st) {
     (void)hipGetLastError();   // report this launch's own error, not an earlier call's
     if (!p.n) return hipSuccess;
-    if (!p.ctr) return hipErrorInvalidValue;
+    if (!p.ctr || (p.gro && !p.dverdict)) return hipErrorInvalidValue;
     // four workgroups per CU at the most, persistent over the frames (a quarter-wave per run of frames)
     const uint64_t rows = kThreads / kGroup, want = (p.n + rows * kRun - 1) / (rows * kRun);
     const uint64_t most = (uint64_t)cus * 4;
     const int grid = (int)(want < most ? want : most);
-    if (p.dverdict) {
+    if (p.gro) {
+        g_last_route_gro.store((int)Route::kGro, std::memory_order_relaxed);
+        hipLaunchKernelGGL((rxr_kernel<kThreads, true, true>), dim3(grid), dim3(kThreads), 0, st, p);
+    } else if (p.dverdict) {
         g_last_route_l4.store((int)Route::kGeneralL4, std::memory_order_relaxed);
         hipLaunchKernelGGL((rxr_kernel<kThreads, true>), dim3(grid), dim3(kThreads), 0, st, p);
     } else {
@@ -564,15 +632,15 @@ hipError_t launch_verdict(const RParams &p, hipStream_t st) {
     if (!p.dverdict || !p.counts) return hipErrorInvalidValue;
     const uint64_t nb = plan_blocks(p.n);
     if (nb > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rxd_verdict_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p);
+    if (p.gro) hipLaunchKernelGGL(rxd_verdict_kernel<true>, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p);
+    else hipLaunchKernelGGL(rxd_verdict_kernel<false>, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p);
     return hipGetLastError();
 }
 
-hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st) {
+hipError_t launch_plan_front(const RParams &p, const Scratch &s, hipStream_t st) {
     (void)hipGetLastError();
-    if (!p.n) return hipSuccess;
     const uint64_t nb = plan_blocks(p.n);
-    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    if (!p.n || nb > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 g((unsigned)nb), t(kPlanThreads);
     hipError_t e;
     hipLaunchKernelGGL(rxr_classify_kernel, g, t, 0, st, p, s);
@@ -580,15 +648,42 @@ hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st) {
     hipLaunchKernelGGL(rxr_insert_kernel, g, t, 0, st, p, s);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(rxr_link_kernel, g, t, 0, st, p, s);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rxr_decide_kernel, g, t, 0, st, p, s);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_plan_decide(const RParams &p, const Scratch &s, const gro::GScratch *gs, hipStream_t st) {
+    (void)hipGetLastError();
+    const uint64_t nb = plan_blocks(p.n);
+    if (!p.n || nb > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)nb), t(kPlanThreads);
+    if (gs) hipLaunchKernelGGL(rxr_decide_kernel<true>, g, t, 0, st, p, s, *gs);
+    else hipLaunchKernelGGL(rxr_decide_kernel<false>, g, t, 0, st, p, s, gro::GScratch{});
+    return hipGetLastError();
+}
+
+hipError_t launch_plan_back(const RParams &p, const Scratch &s, hipStream_t st) {
+    (void)hipGetLastError();
+    const uint64_t nb = plan_blocks(p.n);
+    if (!p.n || nb > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)nb), t(kPlanThreads);
+    hipError_t e;
     hipLaunchKernelGGL(rxr_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(rxr_place_kernel, g, t, 0, st, p, s);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(rxr_finish_kernel, g, t, 0, st, p, s);
     return hipGetLastError();
+}
+
+// classify, insert, link; decide; the scan of the totals, place, finish
+hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st) {
+    (void)hipGetLastError();
+    if (!p.n) return hipSuccess;
+    if (plan_blocks(p.n) > 0x7fffffffull) return hipErrorInvalidValue;
+    hipError_t e;
+    if ((e = launch_plan_front(p, s, st)) != hipSuccess) return e;
+    if ((e = launch_plan_decide(p, s, nullptr, st)) != hipSuccess) return e;
+    return launch_plan_back(p, s, st);
 }
 
 }  // namespace rxr

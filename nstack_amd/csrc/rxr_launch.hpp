@@ -34,6 +34,8 @@ struct RParams {
     uint32_t *dverdict;        // n words: the build's per-datagram accumulators, then the verdicts
     unsigned long long *bad;   // may be null
     uint32_t bad_mask;
+    // include/nstack_gro.h: the build and the verdict launch of the coalescing forms (needs dverdict)
+    uint32_t gro;
 };
 
 // The plan's scratch (device memory that lives on the stream between the launches).
@@ -93,9 +95,10 @@ inline Scratch carve(void *mem, uint64_t n) {
 // The part of the scratch the plan wants zeroed before its first launch: acc and the table (adjacent).
 inline uint64_t zeroed_bytes(uint64_t n) { return n * sizeof(Acc) + table_size(n) * sizeof(Entry); }
 
-enum class Route { kNone, kGeneral, kGeneralL4 };
+enum class Route { kNone, kGeneral, kGeneralL4, kGro };
 Route last_launch();      // what the last plain launch_build of this process launched (tests)
 Route last_launch_l4();   // what the last launch_build with p.dverdict launched (tests)
+Route last_launch_gro();  // what the last launch_build with p.gro launched (tests)
 
 // The plan of p.n frames: the launches of include/nstack_rxr.h on `st`. `s` is carved scratch whose
 // zeroed part has been zeroed on the stream.
@@ -103,11 +106,13 @@ hipError_t launch_plan(const RParams &p, const Scratch &s, hipStream_t st);
 
 // Copies the delivered frames' bytes on a grid of at most `cus` workgroups; needs p.ctr. With
 // p.dverdict (zeroed on the stream) the summing instantiation runs: every frame also adds the
-// one's-complement sum of the bytes it stores to dverdict[dgi[i]].
+// one's-complement sum of the bytes it stores to dverdict[dgi[i]]. With p.gro as well the coalescing
+// instantiation runs (include/nstack_gro.h rule 4).
 hipError_t launch_build(const RParams &p, int cus, hipStream_t st);
 
 // The verdict word of every datagram k < min(counts[0], n) from dverdict[k] as launch_build left it
-// and the delivered header in `out`; *bad (zeroed on the stream) counts verdict & bad_mask.
+// and the delivered header in `out`; *bad (zeroed on the stream) counts verdict & bad_mask. With
+// p.gro it is the finishing launch of include/nstack_gro.h: a merged datagram gets its TCP checksum.
 hipError_t launch_verdict(const RParams &p, hipStream_t st);
 
 }  // namespace rxr
