@@ -40,7 +40,11 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "tx_tso_count", "tx_tso_plan_dev", "tx_tso_dev", "tx_tso_host", "tso_last_launch", "TSO_EXPORTS",
            "TSO_F_ID_FIXED", "TSO_F_MSS_ONE", "TSO_SEGMENTED",
            "rx_gro_plan_host", "rx_gro_plan_dev", "rx_gro_dev", "rx_gro_host", "gro_last_launch", "GRO_EXPORTS",
-           "GRO_CAND", "GRO_MERGED", "GRO_FIN", "GRO_PSH", "GROD_MERGED"]
+           "GRO_CAND", "GRO_MERGED", "GRO_FIN", "GRO_PSH", "GROD_MERGED",
+           "rx_demux_plan_host", "rx_demux_plan_dev", "rx_demux_dev", "rx_demux_host", "dmx_last_launch",
+           "dmx_last_host_chunks", "dmx_key", "DMX_EXPORTS", "DMX_DROPPED", "DMX_NO_PROTO", "DMX_SHORT", "DMX_CTRL",
+           "DMX_NO_SOCK", "DMX_QUEUED", "DMX_NO_ROOM", "DMX_DELIVERED", "DMX_NONE32", "DMX_NONE64", "DMX_MAX_SOCKS",
+           "DMX_REC_HDR", "DMX_SCRATCH_PER_N", "DMX_SCRATCH_PER_S", "DMX_SCRATCH_FIXED"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -119,6 +123,15 @@ TSO_SEGMENTED = 0x400
 GRO_EXPORTS = ["ip_rx_gro_plan_host", "ip_rx_gro_plan_dev", "ip_rx_gro_dev", "ip_rx_gro_host", "fcs_debug_gro_last_launch"]
 GRO_CAND, GRO_MERGED, GRO_FIN, GRO_PSH = 0x1000, 0x2000, 0x4000, 0x8000
 GROD_MERGED = 0x400
+
+# include/nstack_dmx.h — one-pass RX demultiplexing (its own list, as GRO_EXPORTS)
+DMX_EXPORTS = ["ip_rx_demux_plan_host", "ip_rx_demux_plan_dev", "ip_rx_demux_dev", "ip_rx_demux_host",
+               "fcs_debug_dmx_last_launch", "fcs_debug_dmx_last_host_chunks"]
+DMX_DROPPED, DMX_NO_PROTO, DMX_SHORT, DMX_CTRL = 0x001, 0x002, 0x004, 0x008
+DMX_NO_SOCK, DMX_QUEUED, DMX_NO_ROOM, DMX_DELIVERED = 0x010, 0x020, 0x040, 0x080
+DMX_NONE32, DMX_NONE64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+DMX_MAX_SOCKS, DMX_REC_HDR = 65536, 24
+DMX_SCRATCH_PER_N, DMX_SCRATCH_PER_S, DMX_SCRATCH_FIXED = 26, 48, 4096
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -289,6 +302,12 @@ def _bind(path: str) -> ctypes.CDLL:
         "ip_rx_gro_dev": (i32, [vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, vp]),
         "ip_rx_gro_host": (c.c_int64, [vp, u64, vp, vp, u64, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, u32, vp, vp]),
         "fcs_debug_gro_last_launch": (i32, [c.c_char_p, u64]),
+        "ip_rx_demux_plan_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
+        "ip_rx_demux_plan_dev": (i32, [vp, u64, vp, vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "ip_rx_demux_dev": (i32, [vp, u64, vp, vp, vp, u64, vp, vp, u32, vp, u64, vp, vp]),
+        "ip_rx_demux_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
+        "fcs_debug_dmx_last_launch": (i32, [c.c_char_p, u64]),
+        "fcs_debug_dmx_last_host_chunks": (c.c_int64, [vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1075,3 +1094,65 @@ def gro_last_launch() -> str:
     buf = ctypes.create_string_buffer(32)
     _check(load().fcs_debug_gro_last_launch(buf, 32), "fcs_debug_gro_last_launch")
     return buf.value.decode()
+
+
+# ---- one-pass RX demultiplexing (include/nstack_dmx.h) ----
+def dmx_key(proto: int, port: int, addr: int) -> int:
+    """A bind key: proto 6 or 17, the host-order port and the host-order IPv4 address."""
+    return (proto << 48) | (port << 32) | addr
+
+
+def rx_demux_plan_host(out, out_bytes: int, doff, dlen, n: int, bind, nsock: int, dstat, dsock, rec, sbase, scnt,
+                       dverdict=None, drop_mask: int = 0, align: int = 8) -> int:
+    """The plan of n datagrams against bind[nsock] (u64 keys, dmx_key): dstat, dsock, rec per datagram,
+    sbase[nsock + 1] and scnt[nsock] per socket. Host arithmetic, no GPU. Returns the record count;
+    sbase[nsock] sizes q."""
+    return _check(load().ip_rx_demux_plan_host(_ptr(out), out_bytes, _ptr(doff), _ptr(dlen), _ptr(dverdict), n, _ptr(bind),
+                                               _u32(nsock, "nsock"), _u32(drop_mask, "drop_mask"), _u32(align, "align"),
+                                               _ptr(dstat), _ptr(dsock), _ptr(rec), _ptr(sbase), _ptr(scnt)),
+                  "ip_rx_demux_plan_host")
+
+
+def rx_demux_plan_dev(out, out_bytes: int, doff, dlen, counts, n: int, bind, nsock: int, dstat, dsock, rec, sbase, scnt,
+                      qcounts, dverdict=None, drop_mask: int = 0, align: int = 8, stream=None) -> None:
+    """The same arrays in device memory (the first min(counts[0], n) datagrams), plus qcounts[4] =
+    {records, bytes, no socket, dropped} (u64); asynchronous on `stream`."""
+    _check(load().ip_rx_demux_plan_dev(_ptr(out), out_bytes, _ptr(doff), _ptr(dlen), _ptr(dverdict), _ptr(counts), n,
+                                       _ptr(bind), _u32(nsock, "nsock"), _u32(drop_mask, "drop_mask"), _u32(align, "align"),
+                                       _ptr(dstat), _ptr(dsock), _ptr(rec), _ptr(sbase), _ptr(scnt), _ptr(qcounts),
+                                       _stream(stream)),
+           "ip_rx_demux_plan_dev")
+
+
+def rx_demux_dev(out, out_bytes: int, doff, dlen, counts, n: int, pstat, rec, q, q_bytes: int, align: int = 8, dstat=None,
+                 stream=None) -> None:
+    """Writes the nstack_dgram records of the plan into q (aligned to `align`); dstat gets the final
+    words (DMX_DELIVERED / DMX_NO_ROOM). Device arrays; asynchronous on `stream`."""
+    _check(load().ip_rx_demux_dev(_ptr(out), out_bytes, _ptr(doff), _ptr(dlen), _ptr(counts), n, _ptr(pstat), _ptr(rec),
+                                  _u32(align, "align"), _ptr(q), q_bytes, _ptr(dstat), _stream(stream)),
+           "ip_rx_demux_dev")
+
+
+def rx_demux_host(out, out_bytes: int, doff, dlen, n: int, bind, nsock: int, q, q_bytes: int, dverdict=None,
+                  drop_mask: int = 0, align: int = 8, dstat=None, dsock=None, rec=None, sbase=None, scnt=None) -> int:
+    """Host form: host memory in and out, built on the GPU in pipeline chunks. Returns the record
+    count; dmx_last_host_chunks() reports its chunks."""
+    return _check(load().ip_rx_demux_host(_ptr(out), out_bytes, _ptr(doff), _ptr(dlen), _ptr(dverdict), n, _ptr(bind),
+                                          _u32(nsock, "nsock"), _u32(drop_mask, "drop_mask"), _u32(align, "align"), _ptr(q),
+                                          q_bytes, _ptr(dstat), _ptr(dsock), _ptr(rec), _ptr(sbase), _ptr(scnt)),
+                  "ip_rx_demux_host")
+
+
+def dmx_last_launch() -> str:
+    """The kernel the last demultiplexing build launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_dmx_last_launch(buf, 32), "fcs_debug_dmx_last_launch")
+    return buf.value.decode()
+
+
+def dmx_last_host_chunks() -> list:
+    """The datagrams of each chunk the calling thread's last rx_demux_host cut its batch into."""
+    k = _check(load().fcs_debug_dmx_last_host_chunks(None, 0), "fcs_debug_dmx_last_host_chunks")
+    buf = (ctypes.c_uint64 * max(k, 1))()
+    load().fcs_debug_dmx_last_host_chunks(buf, k)
+    return list(buf[:k])
