@@ -65,7 +65,7 @@ static_assert(65535 <= kInBytes, "a datagram fits a chunk");
 static_assert(dmx::kRecHdr + 127 - 28 <= 124, "a chunk's records fit its output buffer");
 
 struct DmxPipe;   // names this engine's pipelines (host_pipe.hpp)
-thread_local std::vector<uint64_t> t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
+thread_local ChunkLog t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
 enum { kIn, kOff, kLen, kStat, kRec, kOut, kCnt };   // host_pipe.hpp's stage_h2d wants frames, offsets and lengths first
 const std::vector<BufSpec> kBufs = {{kInBytes + 64, "dmx staging"}, {kChunkDgs * 8, "doff"},   {kChunkDgs * 4, "dlen"},
                                     {kChunkDgs * 4, "pstat"},       {kChunkDgs * 8, "rec"},    {kOutBytes, "dmx records"},
@@ -85,7 +85,7 @@ int run_host(const uint8_t *out, uint64_t n, const HostPlan &hp, uint32_t align,
         if (c.e == i)   // a datagram always fits a chunk (above): cannot happen
             return fcs::set_error(EINVAL, "datagram %llu exceeds the host chunk", (unsigned long long)i);
         const uint64_t np = c.e - i;
-        t_chunks.push_back(np);
+        t_chunks.add(np);
         uint64_t ob = 0;
         for (uint64_t x = 0; x < np; x++) {
             const bool queued = hp.dstat[i + x] & dmx::kQueued;
@@ -186,15 +186,11 @@ int ip_rx_demux_plan_dev(const void *out, uint64_t out_bytes, const uint64_t *do
     p.scnt = scnt;
     p.qcounts = qcounts;
     // scratch that lives on the stream, between the launches
-    void *mem = nullptr;
-    HIPTRY(hipMallocAsync(&mem, dmx::scratch_bytes(n, S), st), "hipMallocAsync(plan scratch)");
-    hipError_t e = hipMemsetAsync(mem, 0, dmx::zero_bytes(S), st);
-    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)mem + dmx::zero_bytes(S), 0xff, dmx::ones_bytes(n, S), st);
-    if (e == hipSuccess) e = dmx::launch_plan(p, dmx::carve(mem, n, S), st);
-    const hipError_t e2 = hipFreeAsync(mem, st);
-    HIPTRY(e, "launching the plan kernels");
-    HIPTRY(e2, "hipFreeAsync(plan scratch)");
-    return 0;
+    return with_stream_scratch(dmx::scratch_bytes(n, S), st, [&](void *mem) {
+        hipError_t e = hipMemsetAsync(mem, 0, dmx::zero_bytes(S), st);
+        if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)mem + dmx::zero_bytes(S), 0xff, dmx::ones_bytes(n, S), st);
+        return e == hipSuccess ? dmx::launch_plan(p, dmx::carve(mem, n, S), st) : e;
+    });
 }
 
 int ip_rx_demux_dev(const void *out, uint64_t out_bytes, const uint64_t *doff, const uint32_t *dlen, const uint64_t *counts,
@@ -287,8 +283,7 @@ int fcs_debug_dmx_last_launch(char *out, uint64_t cap) {
 }
 
 int64_t fcs_debug_dmx_last_host_chunks(uint64_t *dgs, uint64_t cap) {
-    for (uint64_t k = 0; dgs && k < cap && k < t_chunks.size(); k++) dgs[k] = t_chunks[k];
-    return (int64_t)t_chunks.size();
+    return t_chunks.report(dgs, cap);
 }
 
 }  // extern "C"

@@ -4,9 +4,8 @@
 //
 // The build kernel. After the plan every datagram is independent: it writes one record at
 // q + rec[k]. A QUARTER-WAVE takes a datagram; rows take runs of kRun consecutive datagrams from a
-// zeroed device counter, as rxr_kernel's rows take frames. The copy loop is rxr_kernel's, written
-// again here (lifting it into a shared header would change the code object of the three existing
-// build instantiations; DESIGN §3.18 leaves that to a follow-up):
+// zeroed device counter (row_work.hpp). The copy loop is rxr_kernel's, written again here (one shared
+// loop changed the code of rxr_kernel's plain and summing builds and slowed them: DESIGN §3.19):
 //   * The 24-byte header goes out as six aligned dword stores: the record start is a multiple of
 //     align >= 8 behind a q aligned to it.
 //   * The payload destination is rec + 24, so its phase on the 16-byte grid is 8 (0 or 8 at
@@ -31,23 +30,17 @@
 #include <atomic>
 
 #include "dmx_launch.hpp"
+#include "row_work.hpp"
 
 namespace dmx {
 
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-template <typename T>
-__device__ __forceinline__ T gload(uint64_t addr) {
-    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(addr);
-}
-template <typename T>
-__device__ __forceinline__ void gstore(uint64_t addr, T v) {
-    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
-}
-
-constexpr int kGroup = 16;     // lanes per datagram
-constexpr uint64_t kRun = 8;   // datagrams a row takes from the work counter at a time
-constexpr int kFlight = 4;     // 16-byte pieces a lane has in flight
+using plan::block_scan_incl;
+using row::gload;
+using row::gstore;
+using row::kFlight;
+using row::kGroup;
+using row::u32x4a4;
+using row::kRun;
 
 __device__ __forceinline__ uint64_t count_of(const DParams &p) {
     const uint64_t m = p.counts[0];
@@ -56,25 +49,10 @@ __device__ __forceinline__ uint64_t count_of(const DParams &p) {
 
 template <int NT>
 __global__ __launch_bounds__(NT) void dmx_kernel(DParams p) {
-    const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
+    const int j = threadIdx.x & (kGroup - 1);
     const uint64_t m = count_of(p);
-    // this row's run of datagrams [cur, end), taken from p.ctr
-    uint64_t cur = 0, end = 0;
-    auto take = [&](bool want) {   // wave-uniform call: every row with `want` gets the next run
-        const uint64_t mk = __ballot(want && j == 0);
-        if (mk == 0) return;
-        const int leader = __ffsll((unsigned long long)mk) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(p.ctr, (unsigned long long)__popcll(mk) * kRun);
-        base = __shfl(base, leader, 64);
-        const uint64_t before = mk & ((1ull << (lane & ~(kGroup - 1))) - 1ull);   // wanting rows in front of this one
-        if (want) {
-            cur = base + (uint64_t)__popcll(before) * kRun;
-            end = cur + kRun < p.n ? cur + kRun : p.n;
-        }
-    };
-
-    auto dgram = [&](uint64_t k) {
+    // a row takes runs of datagrams from p.ctr
+    row::for_each_item(p.ctr, p.n, [&](uint64_t k) {
         uint32_t fin = 0u;   // entries [m, n) are zero
         if (k < m) {
             const uint32_t st = p.pstat[k];
@@ -146,15 +124,7 @@ __global__ __launch_bounds__(NT) void dmx_kernel(DParams p) {
             }
         }
         if (j == 0 && p.dstat != nullptr) p.dstat[k] = fin;
-    };
-
-    bool done = false;
-    while (true) {
-        take(!done && cur >= end);
-        if (!done && cur >= p.n) done = true;
-        if (__all(done)) break;
-        if (!done) dgram(cur++);
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -176,29 +146,25 @@ __global__ __launch_bounds__(kPlanThreads) void dmx_table_kernel(DParams p, Scra
     if (i >= p.S) return;
     const unsigned long long key = p.bind[i];
     if (!key_valid(key)) return;   // matches nothing
-    const uint64_t mask = s.tsize - 1;
-    uint64_t h = hash_of(key) & mask;
-    for (uint64_t t = 0; t < s.tsize; t++) {
+    plan::probe(s.tsize, hash_of(key), [&](uint64_t h) {
         const unsigned long long old = atomicCAS(&s.tkey[h], 0ull, key);
-        if (old == 0ull || old == key) {
-            atomicMin(&s.tidx[h], (uint32_t)i);
-            return;
-        }
-        h = (h + 1) & mask;
-    }
+        if (old != 0ull && old != key) return false;
+        atomicMin(&s.tidx[h], (uint32_t)i);
+        return true;
+    });
 }
 
 // The lowest index of `key`, or kNone32. At most tsize probes; an empty entry ends every miss.
 __device__ __forceinline__ uint32_t find(const Scratch &s, uint64_t key) {
-    const uint64_t mask = s.tsize - 1;
-    uint64_t h = hash_of(key) & mask;
-    for (uint64_t t = 0; t < s.tsize; t++) {
+    uint32_t idx = kNone32;
+    plan::probe(s.tsize, hash_of(key), [&](uint64_t h) {
         const unsigned long long c = s.tkey[h];
-        if (c == 0ull) return kNone32;
-        if (c == key) return s.tidx[h];
-        h = (h + 1) & mask;
-    }
-    return kNone32;
+        if (c == 0ull) return true;
+        if (c != key) return false;
+        idx = s.tidx[h];
+        return true;
+    });
+    return idx;
 }
 
 // 2. Rules 1-6 for datagram k; the counters (integer adds commute: no order dependence).
@@ -241,24 +207,6 @@ __global__ __launch_bounds__(kPlanThreads) void dmx_classify_kernel(DParams p, S
         if (wg[1]) atomicAdd((unsigned long long *)p.qcounts + 2, (unsigned long long)wg[1]);
         if (wg[2]) atomicAdd((unsigned long long *)p.qcounts + 3, (unsigned long long)wg[2]);
     }
-}
-
-// Inclusive scan over the workgroup; total: the workgroup's sum.
-template <class T>
-__device__ __forceinline__ T block_scan_incl(T v, T *sh, T &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kPlanThreads; o <<= 1) {
-        const T add = t >= o ? sh[t - o] : (T)0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    const T r = sh[t];
-    total = sh[kPlanThreads - 1];
-    __syncthreads();   // sh is free for the next call
-    return r;
 }
 
 // 3a. The digit histogram of a tile: hist[digit * tiles + tile]. A key of kNone32 is no element.
@@ -372,15 +320,7 @@ __global__ __launch_bounds__(kPlanThreads) void dmx_size_totals_kernel(DParams p
 // 4b. One workgroup: the block totals become the sums of the blocks in front; sbase[S] and qcounts[1].
 __global__ __launch_bounds__(kPlanThreads) void dmx_scan_totals_kernel(DParams p, Scratch s, uint64_t nb) {
     __shared__ uint64_t sh[kPlanThreads];
-    uint64_t base = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += kPlanThreads) {
-        const uint64_t b = b0 + threadIdx.x;
-        const uint64_t v = b < nb ? s.tot[b] : 0ull;
-        uint64_t tot;
-        const uint64_t inc = block_scan_incl(v, sh, tot);
-        if (b < nb) s.tot[b] = base + inc - v;
-        base += tot;
-    }
+    const uint64_t base = plan::scan_totals(s.tot, nb, sh);
     if (threadIdx.x == 0) {
         p.sbase[p.S] = base;
         p.qcounts[1] = base;
@@ -392,8 +332,7 @@ __global__ __launch_bounds__(kPlanThreads) void dmx_place_kernel(DParams p, Scra
     __shared__ uint64_t sh[kPlanThreads];
     const uint64_t pos = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
     const uint64_t v = size_at(s, keys, idx, pos, p.n);
-    uint64_t tot;
-    const uint64_t at = s.tot[blockIdx.x] + block_scan_incl(v, sh, tot) - v;
+    const uint64_t at = s.tot[blockIdx.x] + plan::block_scan_excl(v, sh);
     if (pos < p.n && keys[pos] != kNone32 && idx[pos] < p.n) p.rec[idx[pos]] = at;
 }
 
@@ -442,30 +381,23 @@ hipError_t launch_plan(const DParams &p, const Scratch &s, hipStream_t st) {
     const uint64_t nb = plan_blocks(p.n), nt = tiles(p.n);
     if (nb > 0x7fffffffull || p.n >= kMaxDgs) return hipErrorInvalidValue;
     const dim3 t(kPlanThreads), g((unsigned)nb), gt((unsigned)nt);
-    hipError_t e;
-#define DMX_LAUNCH(...)                                          \
-    do {                                                         \
-        hipLaunchKernelGGL(__VA_ARGS__);                         \
-        if ((e = hipGetLastError()) != hipSuccess) return e;     \
-    } while (0)
-    if (p.S) DMX_LAUNCH(dmx_table_kernel, dim3((unsigned)plan_blocks(p.S)), t, 0, st, p, s);
-    DMX_LAUNCH(dmx_classify_kernel, g, t, 0, st, p, s);
-    DMX_LAUNCH(dmx_hist_kernel, gt, t, 0, st, s.skey, 0u, s.hist, p.n, nt);
-    DMX_LAUNCH(dmx_scan_hist_kernel, dim3(1), t, 0, st, s.hist, nt * 256);
-    DMX_LAUNCH(dmx_scatter_kernel, gt, t, 0, st, s.skey, (const uint32_t *)nullptr, 0u, s.hist, s.key1, s.idx1, p.n, nt);
+    if (p.S) PLAN_LAUNCH(dmx_table_kernel, dim3((unsigned)plan_blocks(p.S)), t, 0, st, p, s);
+    PLAN_LAUNCH(dmx_classify_kernel, g, t, 0, st, p, s);
+    PLAN_LAUNCH(dmx_hist_kernel, gt, t, 0, st, s.skey, 0u, s.hist, p.n, nt);
+    PLAN_LAUNCH(dmx_scan_hist_kernel, dim3(1), t, 0, st, s.hist, nt * 256);
+    PLAN_LAUNCH(dmx_scatter_kernel, gt, t, 0, st, s.skey, (const uint32_t *)nullptr, 0u, s.hist, s.key1, s.idx1, p.n, nt);
     const uint32_t *keys = s.key1, *idx = s.idx1;
     if (p.S > 256u) {
-        DMX_LAUNCH(dmx_hist_kernel, gt, t, 0, st, s.key1, 8u, s.hist, p.n, nt);
-        DMX_LAUNCH(dmx_scan_hist_kernel, dim3(1), t, 0, st, s.hist, nt * 256);
-        DMX_LAUNCH(dmx_scatter_kernel, gt, t, 0, st, s.key1, s.idx1, 8u, s.hist, s.key2, s.idx2, p.n, nt);
+        PLAN_LAUNCH(dmx_hist_kernel, gt, t, 0, st, s.key1, 8u, s.hist, p.n, nt);
+        PLAN_LAUNCH(dmx_scan_hist_kernel, dim3(1), t, 0, st, s.hist, nt * 256);
+        PLAN_LAUNCH(dmx_scatter_kernel, gt, t, 0, st, s.key1, s.idx1, 8u, s.hist, s.key2, s.idx2, p.n, nt);
         keys = s.key2;
         idx = s.idx2;
     }
-    DMX_LAUNCH(dmx_size_totals_kernel, g, t, 0, st, p, s, keys, idx);
-    DMX_LAUNCH(dmx_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
-    DMX_LAUNCH(dmx_place_kernel, g, t, 0, st, p, s, keys, idx);
-    if (p.S) DMX_LAUNCH(dmx_sbase_kernel, dim3((unsigned)plan_blocks(p.S)), t, 0, st, p, keys, idx);
-#undef DMX_LAUNCH
+    PLAN_LAUNCH(dmx_size_totals_kernel, g, t, 0, st, p, s, keys, idx);
+    PLAN_LAUNCH(dmx_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
+    PLAN_LAUNCH(dmx_place_kernel, g, t, 0, st, p, s, keys, idx);
+    if (p.S) PLAN_LAUNCH(dmx_sbase_kernel, dim3((unsigned)plan_blocks(p.S)), t, 0, st, p, keys, idx);
     return hipSuccess;
 }
 

@@ -5,6 +5,7 @@
 
 #include "../../include/nstack_dmx.h"
 #include "dmx_plan.hpp"
+#include "plan_prims.hpp"
 
 namespace dmx {
 
@@ -32,7 +33,10 @@ struct DParams {
 };
 
 constexpr int kThreads = 512;        // dmx_kernel: a quarter-wave per datagram
-constexpr int kPlanThreads = 256;    // the plan kernels
+using plan::kPlanThreads;            // the plan kernels
+using plan::plan_blocks;
+using plan::table_size;              // of the bind table: >= 2 S
+using plan::up16;
 constexpr uint64_t kTile = 1024;     // elements of a partition tile: four rounds of kPlanThreads
 
 // The plan's scratch (device memory that lives on the stream between the launches).
@@ -48,14 +52,7 @@ struct Scratch {
     uint64_t *tot;              // blocks: the block totals of the record sizes in sorted order, then their scan
 };
 
-inline uint64_t table_size(uint64_t S) {
-    uint64_t t = 16;
-    while (t < 2 * S) t <<= 1;
-    return t;
-}
-inline uint64_t plan_blocks(uint64_t n) { return (n + kPlanThreads - 1) / kPlanThreads; }
 inline uint64_t tiles(uint64_t n) { return (n + kTile - 1) / kTile; }
-inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 // Bytes of scratch, and the carving of one allocation of that size (16-byte aligned parts). The parts
 // the plan wants filled in front of its first launch lie first: the table keys (zero), then tidx,
 // key1 and key2 (all ones).
@@ -66,6 +63,7 @@ inline uint64_t scratch_bytes(uint64_t n, uint64_t S) {
 }
 // The bound include/nstack_dmx.h states: 24 bytes of arrays, one of histogram and 1/32 of totals per
 // n; 12 bytes per table entry, fewer than 4 S of them (or 16).
+static_assert(kPlanThreads == 256, "kPlanThreads = 256 is behind the 1/32 of totals per n");
 static_assert(DMX_SCRATCH_PER_N >= 24 + 1 + 1 && DMX_SCRATCH_PER_S >= 4 * 12 && DMX_SCRATCH_FIXED >= 16 * 12 + 9 * 16 + 1024 + 8,
               "the scratch bound of include/nstack_dmx.h");
 inline uint64_t scratch_bound(uint64_t n, uint64_t S) { return n * DMX_SCRATCH_PER_N + S * DMX_SCRATCH_PER_S + DMX_SCRATCH_FIXED; }

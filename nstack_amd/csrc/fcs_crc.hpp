@@ -9,10 +9,11 @@
 
 #include "fcs_launch.hpp"
 #include "fcs_tables.hpp"
+#include "row_work.hpp"
 
 namespace fcs {
 
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+using row::u32x4a4;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Frame slots (quarter-waves) per workgroup of NT threads; LDS (150 KiB) -> 1 WG per CU.
@@ -23,16 +24,7 @@ constexpr int kSingleMaskWords = kSingleMaxLead / 4;   // SINGLE variant: front-
 #define FCS_CHAINS 2                               // independent chains per lane (2 or 4)
 #endif
 
-// Loads through address space 1 (global): flat loads would also count on lgkmcnt and make every
-// LDS wait drain the prefetched chunk loads.
-template <typename T>
-__device__ __forceinline__ T gload(uint64_t addr) {
-#ifdef FCS_NT   // measurement-only build: non-temporal (nt) frame loads
-    return __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) T *>(addr));
-#else
-    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(addr);
-#endif
-}
+using row::gload;   // loads through address space 1 (global), row_work.hpp
 
 // a ^ b ^ c in one VALU op: gfx950's v_bitop3_b32 with truth table 0x96.
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {

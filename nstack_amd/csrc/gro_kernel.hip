@@ -29,19 +29,9 @@ namespace gro {
 using fcs::gload;
 using rxr::Entry;
 using rxr::kNone32;
-using rxr::kPlanThreads;
+using plan::kPlanThreads;
 using rxr::RParams;
 using rxr::Scratch;
-
-__device__ __forceinline__ uint64_t hash_of(uint32_t src, uint32_t dst, uint32_t ports, uint32_t x) {
-    uint32_t h = src * 0x9E3779B1u ^ dst * 0x85EBCA77u ^ ports * 0xC2B2AE3Du ^ x * 0x27D4EB2Fu;
-    h ^= h >> 15;
-    h *= 0x2C1B3C6Du;
-    h ^= h >> 12;
-    h *= 0x297A2D39u;
-    h ^= h >> 15;
-    return h;
-}
 
 __device__ __forceinline__ bool same_flow(const GRec &a, const GRec &b) {
     return a.src == b.src && a.dst == b.dst && a.ports == b.ports;
@@ -50,16 +40,16 @@ __device__ __forceinline__ bool same_flow(const GRec &a, const GRec &b) {
 // The entry of (me's flow, seq) in the seq table, or tsize when there is none. At most tsize probes;
 // the table holds at most n <= tsize / 2 claims, so an empty entry ends every miss.
 __device__ __forceinline__ uint64_t find_seq(const GScratch &g, const GRec &me, uint32_t seq) {
-    const uint64_t mask = g.tsize - 1;
-    uint64_t h = hash_of(me.src, me.dst, me.ports, seq) & mask;
-    for (uint64_t t = 0; t < g.tsize; t++) {
+    uint64_t at = g.tsize;
+    plan::probe(g.tsize, plan::mix4(me.src, me.dst, me.ports, seq), [&](uint64_t h) {
         const uint32_t c = g.tabs[h].claim;
-        if (c == 0u) return g.tsize;
+        if (c == 0u) return true;
         const GRec o = g.rec[c - 1u];
-        if (same_flow(o, me) && o.seq == seq) return h;
-        h = (h + 1) & mask;
-    }
-    return g.tsize;
+        if (!(same_flow(o, me) && o.seq == seq)) return false;
+        at = h;
+        return true;
+    });
+    return at;
 }
 
 __device__ __forceinline__ uint32_t hlen_of(uint32_t w4) { return ((w4 >> 20) & 0x0fu) * 4u; }
@@ -95,40 +85,29 @@ __global__ __launch_bounds__(kPlanThreads) void gro_insert_kernel(RParams p, GSc
     const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
     if (i >= p.n || !(p.fstat[i] & kCand)) return;
     const GRec me = g.rec[i];
-    const uint64_t mask = g.tsize - 1;
-    uint64_t h = hash_of(me.src, me.dst, me.ports, me.seq) & mask;
-    for (uint64_t t = 0; t < g.tsize; t++) {
+    plan::probe(g.tsize, plan::mix4(me.src, me.dst, me.ports, me.seq), [&](uint64_t h) {
         const uint32_t old = atomicCAS(&g.tabs[h].claim, 0u, (uint32_t)i + 1u);
-        if (old == 0u) {
-            atomicAdd(&g.tabs[h].count, 1u);
-            break;
-        }
-        const GRec o = g.rec[old - 1u];
-        if (same_flow(o, me) && o.seq == me.seq) {
-            atomicAdd(&g.tabs[h].count, 1u);
-            break;
-        }
-        h = (h + 1) & mask;
-    }
-    const uint32_t win = me.seq >> kWinShift;
-    h = hash_of(me.src, me.dst, me.ports, win ^ 0xA5A50000u) & mask;
-    for (uint64_t t = 0; t < g.tsize; t++) {
-        const uint32_t old = atomicCAS(&g.tabg[h].claim, 0u, (uint32_t)i + 1u);
-        uint32_t c = kNone32;
-        if (old == 0u) {
-            c = (uint32_t)i;
-        } else {
+        if (old != 0u) {
             const GRec o = g.rec[old - 1u];
-            if (same_flow(o, me) && (o.seq >> kWinShift) == win) c = old - 1u;
+            if (!(same_flow(o, me) && o.seq == me.seq)) return false;
         }
-        if (c != kNone32) {
-            g.rec[i].group = c;   // no other thread reads or writes this word in this launch
-            atomicMax(&g.acc[c].invmin, kWin - (me.seq & (kWin - 1u)));
-            atomicAdd(&g.acc[c].members, 1u);
-            return;
+        atomicAdd(&g.tabs[h].count, 1u);
+        return true;
+    });
+    const uint32_t win = me.seq >> kWinShift;
+    plan::probe(g.tsize, plan::mix4(me.src, me.dst, me.ports, win ^ 0xA5A50000u), [&](uint64_t h) {
+        const uint32_t old = atomicCAS(&g.tabg[h].claim, 0u, (uint32_t)i + 1u);
+        uint32_t c = (uint32_t)i;
+        if (old != 0u) {
+            const GRec o = g.rec[old - 1u];
+            if (!(same_flow(o, me) && (o.seq >> kWinShift) == win)) return false;
+            c = old - 1u;
         }
-        h = (h + 1) & mask;
-    }
+        g.rec[i].group = c;   // no other thread reads or writes this word in this launch
+        atomicMax(&g.acc[c].invmin, kWin - (me.seq & (kWin - 1u)));
+        atomicAdd(&g.acc[c].members, 1u);
+        return true;
+    });
 }
 
 // 3. Every candidate finds its successor and adds itself up on the group's accumulator.
@@ -203,23 +182,19 @@ __global__ __launch_bounds__(kPlanThreads) void gro_finish_kernel(RParams p, GSc
 hipError_t launch_plan(const RParams &p, const Scratch &s, const GScratch &g, hipStream_t st) {
     (void)hipGetLastError();
     if (!p.n) return hipSuccess;
-    const uint64_t nb = rxr::plan_blocks(p.n);
+    const uint64_t nb = plan::plan_blocks(p.n);
     if (nb > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nb), t(kPlanThreads);
     hipError_t e;
     if ((e = rxr::launch_plan_front(p, s, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_classify_kernel, grid, t, 0, st, p, s, g);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_insert_kernel, grid, t, 0, st, p, g);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_link_kernel, grid, t, 0, st, p, g);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_first_kernel, grid, t, 0, st, p, g);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    PLAN_LAUNCH(gro_classify_kernel, grid, t, 0, st, p, s, g);
+    PLAN_LAUNCH(gro_insert_kernel, grid, t, 0, st, p, g);
+    PLAN_LAUNCH(gro_link_kernel, grid, t, 0, st, p, g);
+    PLAN_LAUNCH(gro_first_kernel, grid, t, 0, st, p, g);
     if ((e = rxr::launch_plan_decide(p, s, &g, st)) != hipSuccess) return e;
     if ((e = rxr::launch_plan_back(p, s, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_finish_kernel, grid, t, 0, st, p, g);
-    return hipGetLastError();
+    PLAN_LAUNCH(gro_finish_kernel, grid, t, 0, st, p, g);
+    return hipSuccess;
 }
 
 }  // namespace gro

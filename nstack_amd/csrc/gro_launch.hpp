@@ -42,14 +42,14 @@ RXR_HD bool coalescible(const GAcc &a) {
 
 // Bytes of scratch behind rxr::scratch_bytes(n), its carving (16-byte aligned parts), and the part
 // the plan wants zeroed before its first launch: acc and both tables (adjacent, in front).
-inline uint64_t scratch_bytes(uint64_t n) { return n * (sizeof(GAcc) + sizeof(GRec)) + 2 * rxr::table_size(n) * sizeof(rxr::Entry); }
-inline uint64_t zeroed_bytes(uint64_t n) { return n * sizeof(GAcc) + 2 * rxr::table_size(n) * sizeof(rxr::Entry); }
+inline uint64_t scratch_bytes(uint64_t n) { return n * (sizeof(GAcc) + sizeof(GRec)) + 2 * plan::table_size(n) * sizeof(rxr::Entry); }
+inline uint64_t zeroed_bytes(uint64_t n) { return n * sizeof(GAcc) + 2 * plan::table_size(n) * sizeof(rxr::Entry); }
 inline GScratch carve(void *mem, uint64_t n) {
     GScratch g;
     uint8_t *p = static_cast<uint8_t *>(mem);
     g.acc = reinterpret_cast<GAcc *>(p);
     p += n * sizeof(GAcc);
-    g.tsize = rxr::table_size(n);
+    g.tsize = plan::table_size(n);
     g.tabs = reinterpret_cast<rxr::Entry *>(p);
     p += g.tsize * sizeof(rxr::Entry);
     g.tabg = reinterpret_cast<rxr::Entry *>(p);

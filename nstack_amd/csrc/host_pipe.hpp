@@ -195,4 +195,29 @@ inline int stage_h2d(Slot &s, hipStream_t st, const uint8_t *arena, const uint64
     return 0;
 }
 
+// A device plan's scratch, which lives on the stream between its launches: hipError_t fn(void *mem)
+// fills it and launches; it is freed on the stream whatever fn returns, and fn's error is the one
+// reported first.
+template <class Fn>
+int with_stream_scratch(uint64_t bytes, hipStream_t st, Fn &&fn) {
+    void *mem = nullptr;
+    HIPTRY(hipMallocAsync(&mem, bytes, st), "hipMallocAsync(plan scratch)");
+    const hipError_t e = fn(mem), e2 = hipFreeAsync(mem, st);
+    HIPTRY(e, "launching the plan kernels");
+    HIPTRY(e2, "hipFreeAsync(plan scratch)");
+    return 0;
+}
+
+// The items of each chunk of this thread's last host call of an engine (tests read it back through
+// the engine's fcs_debug_*_last_host_chunks).
+struct ChunkLog {
+    std::vector<uint64_t> items;
+    void clear() { items.clear(); }
+    void add(uint64_t n) { items.push_back(n); }
+    int64_t report(uint64_t *out, uint64_t cap) const {
+        for (uint64_t k = 0; out && k < cap && k < items.size(); k++) out[k] = items[k];
+        return (int64_t)items.size();
+    }
+};
+
 }  // namespace hostpipe

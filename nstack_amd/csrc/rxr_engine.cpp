@@ -41,6 +41,15 @@ int check_call(uint32_t flags, uint32_t align, uint64_t n) {
     return 0;
 }
 
+// What every plan call checks, host or device.
+int check_plan(uint32_t flags, uint32_t align, uint64_t n, const void *arena, const uint64_t *off, const uint32_t *len,
+               const uint32_t *fstat, const uint64_t *dst, const uint32_t *dgi, const uint64_t *doff, const uint32_t *dlen) {
+    const int rc = check_call(flags, align, n);
+    if (rc) return rc;
+    if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen))) return fcs::set_error(EINVAL, "null pointer");
+    return 0;
+}
+
 // launch_build with the work counter its rows take their frames from, leased from the FCS engine's
 // ring of device `dev` for this launch. With p.dverdict (nstack_rxd.h): the accumulators and *bad are
 // zeroed on the stream in front of the build, and the verdict launch follows it.
@@ -80,7 +89,7 @@ static_assert(8190ull * 74 + 65535 <= kInBytes && 65535 + 127 <= kOutBytes && 81
 static_assert(gro::kMaxMembers * 134ull + 65535 <= kInBytes && gro::kMaxMembers <= kChunkFrames, "a merged datagram fits a chunk");
 
 struct RxrPipe;   // names this engine's pipelines (host_pipe.hpp)
-thread_local std::vector<uint64_t> t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
+thread_local ChunkLog t_chunks;   // the datagrams of each chunk of this thread's last host call (tests)
 enum { kIn, kOff, kLen, kStat, kDst, kDgi, kDoff, kDlen, kOut, kVerd, kCnt };
 const std::vector<BufSpec> kBufs = {{kInBytes + 64, "rxr staging"}, {kChunkFrames * 8, "off"},  {kChunkFrames * 4, "len"},
                                     {kChunkFrames * 4, "fstat"},    {kChunkFrames * 8, "dst"},  {kChunkFrames * 4, "dgi"},
@@ -114,7 +123,7 @@ int64_t run_host(const uint8_t *arena, const uint64_t *off, const HostPlan &hp, 
         if (e == k)   // a datagram always fits a chunk (above): cannot happen
             return fcs::set_error(EINVAL, "datagram %llu exceeds the host chunk", (unsigned long long)k);
         const uint64_t nd = e - k, nf = hp.first[e] - hp.first[k], base = hp.doff[k];
-        t_chunks.push_back(nd);
+        t_chunks.add(nd);
         uint8_t *h_in = s.h<uint8_t>(kIn);
         uint64_t w = 0;
         for (uint64_t q = 0; q < nf; q++) {
@@ -224,39 +233,12 @@ int build_dev(bool l4, bool gro, const void *arena, uint64_t arena_bytes, const 
     return launch(p, dev, cus, st);
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t ether_rx_reasm_plan_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
-                                 uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask,
-                                 uint32_t align, uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff,
-                                 uint32_t *dlen, uint32_t *dlead) {
-    int rc = check_call(flags, align, n);
-    if (rc) return rc;
-    if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen)))
-        return fcs::set_error(EINVAL, "null pointer");
-    uint64_t bad = 0;
-    const int64_t m = rxr::plan_batch((const uint8_t *)arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align,
-                                      fstat, dst, dgi, doff, dlen, dlead, &bad);
-    if (m < 0)
-        return fcs::set_error(EINVAL, "frame %llu [%llu, +%u) outside the %llu-byte arena", (unsigned long long)bad,
-                              (unsigned long long)off[bad], len[bad], (unsigned long long)arena_bytes);
-    return m;
-}
-
-}  // extern "C"
-
-namespace {
-
 // The device plan of nstack_rxr.h, or with gro that of nstack_gro.h.
 int plan_dev(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
              uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat, uint64_t *dst,
              uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint64_t *counts, void *stream) {
-    int rc = check_call(flags, align, n);
+    int rc = check_plan(flags, align, n, arena, off, len, fstat, dst, dgi, doff, dlen);
     if (rc) return rc;
-    if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen)))
-        return fcs::set_error(EINVAL, "null pointer");
     int dev = 0, cus = 0;
     if ((rc = fcs::current_device(&dev, &cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -282,51 +264,23 @@ int plan_dev(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *
     p.dlead = dlead;
     p.counts = counts;
     // scratch that lives on the stream, between the launches
-    void *mem = nullptr;
-    const uint64_t rb = (rxr::scratch_bytes(n) + 15) & ~15ull;   // the coalescing plan's scratch lies behind
-    HIPTRY(hipMallocAsync(&mem, gro ? rb + gro::scratch_bytes(n) : rxr::scratch_bytes(n), st), "hipMallocAsync(plan scratch)");
-    hipError_t e = hipMemsetAsync(mem, 0, rxr::zeroed_bytes(n), st);
-    if (gro) {
+    const uint64_t rb = plan::up16(rxr::scratch_bytes(n));   // the coalescing plan's scratch lies behind
+    return with_stream_scratch(gro ? rb + gro::scratch_bytes(n) : rxr::scratch_bytes(n), st, [&](void *mem) {
+        hipError_t e = hipMemsetAsync(mem, 0, rxr::zeroed_bytes(n), st);
+        if (e != hipSuccess) return e;
+        if (!gro) return rxr::launch_plan(p, rxr::carve(mem, n), st);
         void *gmem = (uint8_t *)mem + rb;
-        if (e == hipSuccess) e = hipMemsetAsync(gmem, 0, gro::zeroed_bytes(n), st);
-        if (e == hipSuccess) e = gro::launch_plan(p, rxr::carve(mem, n), gro::carve(gmem, n), st);
-    } else if (e == hipSuccess) {
-        e = rxr::launch_plan(p, rxr::carve(mem, n), st);
-    }
-    const hipError_t e2 = hipFreeAsync(mem, st);
-    HIPTRY(e, "launching the plan kernels");
-    HIPTRY(e2, "hipFreeAsync(plan scratch)");
-    return 0;
+        e = hipMemsetAsync(gmem, 0, gro::zeroed_bytes(n), st);
+        return e == hipSuccess ? gro::launch_plan(p, rxr::carve(mem, n), gro::carve(gmem, n), st) : e;
+    });
 }
 
-}  // namespace
-
-extern "C" {
-
-int ether_rx_reasm_plan_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
-                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
-                            uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen,
-                            uint32_t *dlead, uint64_t *counts, void *stream) {
-    return plan_dev(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead,
-                    counts, stream);
-}
-
-int ether_rx_reasm_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
-                       uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
-                       const uint64_t *doff, const uint32_t *dlen, void *out, uint64_t out_bytes, uint32_t *fstat,
-                       void *stream) {
-    return build_dev(false, false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, nullptr, out, out_bytes, fstat,
-                     0u, nullptr, nullptr, stream);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The host arithmetic of a plan call: rxr::plan_batch, or with gro gro::plan_batch.
+// A host plan call: the checks, then rxr::plan_batch, or with gro gro::plan_batch.
 int64_t plan_host(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
                   uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat, uint64_t *dst,
                   uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead) {
+    const int rc = check_plan(flags, align, n, arena, off, len, fstat, dst, dgi, doff, dlen);
+    if (rc) return rc;
     uint64_t bad = 0;
     const int64_t m = (gro ? gro::plan_batch : rxr::plan_batch)((const uint8_t *)arena, arena_bytes, off, len, n, flags, verdict,
                                                                 drop_mask, align, fstat, dst, dgi, doff, dlen, dlead, &bad);
@@ -393,9 +347,47 @@ int64_t reasm_host(bool gro, const void *arena, uint64_t arena_bytes, const uint
     return r;
 }
 
+// The host form of nstack_rxd.h and, with gro, of nstack_gro.h: reasm_host with the verdict words, and
+// *bad counted on the host.
+int64_t reasm_l4_host(bool gro, const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                      uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, void *out,
+                      uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint32_t bad_mask,
+                      uint32_t *dverdict, uint64_t *bad) {
+    if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
+    const int64_t m = reasm_host(gro, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat,
+                                 doff, dlen, dlead, dverdict);
+    if (m < 0 || !bad) return m;
+    *bad = 0;
+    for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
+    return m;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t ether_rx_reasm_plan_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
+                                 uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask,
+                                 uint32_t align, uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff,
+                                 uint32_t *dlen, uint32_t *dlead) {
+    return plan_host(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead);
+}
+
+int ether_rx_reasm_plan_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
+                            uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
+                            uint32_t *fstat, uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen,
+                            uint32_t *dlead, uint64_t *counts, void *stream) {
+    return plan_dev(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead,
+                    counts, stream);
+}
+
+int ether_rx_reasm_dev(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
+                       uint32_t flags, const uint32_t *pstat, const uint64_t *dst, const uint32_t *dgi,
+                       const uint64_t *doff, const uint32_t *dlen, void *out, uint64_t out_bytes, uint32_t *fstat,
+                       void *stream) {
+    return build_dev(false, false, arena, arena_bytes, off, len, n, flags, pstat, dst, dgi, doff, dlen, nullptr, out, out_bytes, fstat,
+                     0u, nullptr, nullptr, stream);
+}
 
 int64_t ether_rx_reasm_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len,
                             uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
@@ -418,22 +410,14 @@ int64_t ip_rx_reasm_l4_host(const void *arena, uint64_t arena_bytes, const uint6
                             uint64_t n, uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align,
                             void *out, uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen,
                             uint32_t *dlead, uint32_t bad_mask, uint32_t *dverdict, uint64_t *bad) {
-    if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
-    const int64_t m = reasm_host(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat,
-                                 doff, dlen, dlead, dverdict);
-    if (m < 0 || !bad) return m;
-    *bad = 0;   // counted on the host
-    for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
-    return m;
+    return reasm_l4_host(false, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff, dlen,
+                         dlead, bad_mask, dverdict, bad);
 }
 
 // ---- include/nstack_gro.h ----
 int64_t ip_rx_gro_plan_host(const void *arena, uint64_t arena_bytes, const uint64_t *off, const uint32_t *len, uint64_t n,
                             uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, uint32_t *fstat,
                             uint64_t *dst, uint32_t *dgi, uint64_t *doff, uint32_t *dlen, uint32_t *dlead) {
-    int rc = check_call(flags, align, n);
-    if (rc) return rc;
-    if (!doff || (n && (!arena || !off || !len || !fstat || !dst || !dgi || !dlen))) return fcs::set_error(EINVAL, "null pointer");
     return plan_host(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, fstat, dst, dgi, doff, dlen, dlead);
 }
 
@@ -457,13 +441,8 @@ int64_t ip_rx_gro_host(const void *arena, uint64_t arena_bytes, const uint64_t *
                        uint32_t flags, const uint32_t *verdict, uint32_t drop_mask, uint32_t align, void *out,
                        uint64_t out_bytes, uint32_t *fstat, uint64_t *doff, uint32_t *dlen, uint32_t *dlead, uint32_t bad_mask,
                        uint32_t *dverdict, uint64_t *bad) {
-    if (n && !dverdict) return fcs::set_error(EINVAL, "null dverdict");
-    const int64_t m = reasm_host(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat,
-                                 doff, dlen, dlead, dverdict);
-    if (m < 0 || !bad) return m;
-    *bad = 0;   // counted on the host
-    for (int64_t k = 0; k < m; k++) *bad += (dverdict[k] & bad_mask) != 0u;
-    return m;
+    return reasm_l4_host(true, arena, arena_bytes, off, len, n, flags, verdict, drop_mask, align, out, out_bytes, fstat, doff, dlen,
+                         dlead, bad_mask, dverdict, bad);
 }
 
 // The kernel the last coalescing build launch of this process launched.
@@ -482,8 +461,7 @@ int fcs_debug_rxr_last_launch(char *out, uint64_t cap) {
 }
 
 int64_t fcs_debug_rxr_last_host_chunks(uint64_t *dgs, uint64_t cap) {
-    for (uint64_t k = 0; dgs && k < cap && k < t_chunks.size(); k++) dgs[k] = t_chunks[k];
-    return (int64_t)t_chunks.size();
+    return t_chunks.report(dgs, cap);
 }
 
 }  // extern "C"

@@ -40,24 +40,22 @@
 #include "fcs_crc.hpp"
 #include "ones_fold.hpp"
 #include "gro_launch.hpp"
+#include "row_work.hpp"
 #include "rxr_launch.hpp"
 
 namespace rxr {
 
-using fcs::gload;
-using fcs::u32x4a4;
 using ones::fold64;
 using ones::row_sum;
 using ones::swap16;
-
-constexpr int kGroup = 16;     // lanes per frame
-constexpr uint64_t kRun = 8;   // frames a row takes from the work counter at a time
-constexpr int kFlight = 4;     // 16-byte pieces a lane has in flight
-
-template <typename T>
-__device__ __forceinline__ void gstore(uint64_t addr, T v) {
-    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
-}
+using plan::block_scan_excl;
+using plan::block_scan_incl;
+using row::gload;
+using row::gstore;
+using row::kFlight;
+using row::kGroup;
+using row::kRun;
+using row::u32x4a4;
 
 constexpr uint32_t kNoFlagPos = 0xffffffffu;
 
@@ -98,26 +96,11 @@ __device__ __forceinline__ uint32_t grid_byte(uint64_t a, uint32_t v) { return (
 template <int NT, bool SUM, bool GRO = false>
 __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
     static_assert(SUM || !GRO, "the coalescing build sums");
-    const int lane = threadIdx.x & 63, j = lane & (kGroup - 1);
+    const int j = threadIdx.x & (kGroup - 1);
     const uint32_t T = trailer_of(p.flags);
     const uint64_t arena_bytes = p.arena_bytes;
-    // this row's run of frames [cur, end), taken from p.ctr
-    uint64_t cur = 0, end = 0;
-    auto take = [&](bool want) {   // wave-uniform call: every row with `want` gets the next run
-        const uint64_t m = __ballot(want && j == 0);
-        if (m == 0) return;
-        const int leader = __ffsll((unsigned long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(p.ctr, (unsigned long long)__popcll(m) * kRun);
-        base = __shfl(base, leader, 64);
-        const uint64_t before = m & ((1ull << (lane & ~(kGroup - 1))) - 1ull);   // wanting rows in front of this one
-        if (want) {
-            cur = base + (uint64_t)__popcll(before) * kRun;
-            end = cur + kRun < p.n ? cur + kRun : p.n;
-        }
-    };
-
-    auto frame = [&](uint64_t i) {
+    // a row takes runs of frames from p.ctr
+    row::for_each_item(p.ctr, p.n, [&](uint64_t i) {
         const uint32_t st = p.pstat[i];
         const uint64_t d = p.dst[i];
         uint32_t fin = st;
@@ -246,15 +229,7 @@ __global__ __launch_bounds__(NT) void rxr_kernel(RParams p) {
             }
         }
         if (j == 0 && p.fstat != nullptr) p.fstat[i] = fin;
-    };
-
-    bool done = false;
-    while (true) {
-        take(!done && cur >= end);
-        if (!done && cur >= p.n) done = true;
-        if (__all(done)) break;
-        if (!done) frame(cur++);
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -288,28 +263,18 @@ __device__ __forceinline__ bool same_key(const Rec &a, uint32_t src, uint32_t ds
     return a.src == src && a.dst == dst && (a.w2 & 0x00ffffffu) == idp && (a.w3 & 0xffffu) == o;
 }
 
-__device__ __forceinline__ uint64_t hash_of(uint32_t src, uint32_t dst, uint32_t idp, uint32_t o) {
-    uint32_t h = src * 0x9E3779B1u ^ dst * 0x85EBCA77u ^ idp * 0xC2B2AE3Du ^ o * 0x27D4EB2Fu;
-    h ^= h >> 15;
-    h *= 0x2C1B3C6Du;
-    h ^= h >> 12;
-    h *= 0x297A2D39u;
-    h ^= h >> 15;
-    return h;
-}
-
 // The entry of (key, o), or tsize when there is none. At most tsize probes; the table holds at most
 // n <= tsize / 2 claims, so an empty entry ends every miss.
 __device__ __forceinline__ uint64_t find(const Scratch &s, uint32_t src, uint32_t dst, uint32_t idp, uint32_t o) {
-    const uint64_t mask = s.tsize - 1;
-    uint64_t h = hash_of(src, dst, idp, o) & mask;
-    for (uint64_t t = 0; t < s.tsize; t++) {
+    uint64_t at = s.tsize;
+    plan::probe(s.tsize, plan::mix4(src, dst, idp, o), [&](uint64_t h) {
         const uint32_t c = s.tab[h].claim;
-        if (c == 0u) return s.tsize;
-        if (same_key(s.rec[c - 1u], src, dst, idp, o)) return h;
-        h = (h + 1) & mask;
-    }
-    return s.tsize;
+        if (c == 0u) return true;
+        if (!same_key(s.rec[c - 1u], src, dst, idp, o)) return false;
+        at = h;
+        return true;
+    });
+    return at;
 }
 
 // 1. Rules 1-5 and the key record.
@@ -339,16 +304,12 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_insert_kernel(RParams p, Scr
     const Rec me = s.rec[i];
     if (!(me.w2 & 0x80000000u)) return;
     const uint32_t idp = me.w2 & 0x00ffffffu, o = me.w3 & 0xffffu;
-    const uint64_t mask = s.tsize - 1;
-    uint64_t h = hash_of(me.src, me.dst, idp, o) & mask;
-    for (uint64_t t = 0; t < s.tsize; t++) {
+    plan::probe(s.tsize, plan::mix4(me.src, me.dst, idp, o), [&](uint64_t h) {
         const uint32_t old = atomicCAS(&s.tab[h].claim, 0u, (uint32_t)i + 1u);
-        if (old == 0u || same_key(s.rec[old - 1u], me.src, me.dst, idp, o)) {
-            atomicAdd(&s.tab[h].count, 1u);
-            return;
-        }
-        h = (h + 1) & mask;
-    }
+        if (old != 0u && !same_key(s.rec[old - 1u], me.src, me.dst, idp, o)) return false;
+        atomicAdd(&s.tab[h].count, 1u);
+        return true;
+    });
 }
 
 // 3. Every fragment finds its head and its successor and adds itself up on the head's accumulator.
@@ -374,23 +335,6 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_link_kernel(RParams p, Scrat
     }
     atomicAdd(&a->sumL, (unsigned long long)L);
     if (fault) atomicOr(&a->fault, 1u);
-}
-
-// Inclusive scan over the workgroup; total: the workgroup's sum.
-__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *sh, uint64_t &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kPlanThreads; o <<= 1) {
-        const uint64_t add = t >= o ? sh[t - o] : 0ull;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    const uint64_t r = sh[t];
-    total = sh[kPlanThreads - 1];
-    __syncthreads();   // sh is free for the next call
-    return r;
 }
 
 // 4. Each head decides (rule 6). dgi[i] = 1 on the head frame of a delivered datagram, dst[i] its
@@ -434,8 +378,8 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scr
         p.dst[i] = is ? padded(D, p.align) : 0ull;
     }
     uint64_t tc, tb;
-    block_scan_incl(is, sh, tc);
-    block_scan_incl(is ? padded(D, p.align) : 0ull, sh, tb);
+    block_scan_incl<uint64_t>(is, sh, tc);
+    block_scan_incl<uint64_t>(is ? padded(D, p.align) : 0ull, sh, tb);
     if (threadIdx.x == 0) {
         s.totc[blockIdx.x] = tc;
         s.totb[blockIdx.x] = tb;
@@ -446,6 +390,8 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_decide_kernel(RParams p, Scr
 // doff[m].
 __global__ __launch_bounds__(kPlanThreads) void rxr_scan_totals_kernel(RParams p, Scratch s, uint64_t nb) {
     __shared__ uint64_t sh[kPlanThreads];
+    // both arrays in one loop (the loads of the second overlap the scan of the first), so not two
+    // calls of plan::scan_totals
     uint64_t basec = 0, baseb = 0;
     for (uint64_t b0 = 0; b0 < nb; b0 += kPlanThreads) {
         const uint64_t b = b0 + threadIdx.x;
@@ -475,9 +421,8 @@ __global__ __launch_bounds__(kPlanThreads) void rxr_place_kernel(RParams p, Scra
     __shared__ uint64_t sh[kPlanThreads];
     const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
     const uint64_t is = i < p.n ? p.dgi[i] : 0ull, pb = i < p.n ? p.dst[i] : 0ull;
-    uint64_t tc, tb;
-    const uint64_t k = s.totc[blockIdx.x] + block_scan_incl(is, sh, tc) - is;
-    const uint64_t at = s.totb[blockIdx.x] + block_scan_incl(pb, sh, tb) - pb;
+    const uint64_t k = s.totc[blockIdx.x] + block_scan_excl(is, sh);
+    const uint64_t at = s.totb[blockIdx.x] + block_scan_excl(pb, sh);
     if (i >= p.n) return;
     if (is) {
         p.dgi[i] = (uint32_t)k;
@@ -642,13 +587,10 @@ hipError_t launch_plan_front(const RParams &p, const Scratch &s, hipStream_t st)
     const uint64_t nb = plan_blocks(p.n);
     if (!p.n || nb > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 g((unsigned)nb), t(kPlanThreads);
-    hipError_t e;
-    hipLaunchKernelGGL(rxr_classify_kernel, g, t, 0, st, p, s);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rxr_insert_kernel, g, t, 0, st, p, s);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rxr_link_kernel, g, t, 0, st, p, s);
-    return hipGetLastError();
+    PLAN_LAUNCH(rxr_classify_kernel, g, t, 0, st, p, s);
+    PLAN_LAUNCH(rxr_insert_kernel, g, t, 0, st, p, s);
+    PLAN_LAUNCH(rxr_link_kernel, g, t, 0, st, p, s);
+    return hipSuccess;
 }
 
 hipError_t launch_plan_decide(const RParams &p, const Scratch &s, const gro::GScratch *gs, hipStream_t st) {
@@ -666,13 +608,10 @@ hipError_t launch_plan_back(const RParams &p, const Scratch &s, hipStream_t st) 
     const uint64_t nb = plan_blocks(p.n);
     if (!p.n || nb > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 g((unsigned)nb), t(kPlanThreads);
-    hipError_t e;
-    hipLaunchKernelGGL(rxr_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rxr_place_kernel, g, t, 0, st, p, s);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rxr_finish_kernel, g, t, 0, st, p, s);
-    return hipGetLastError();
+    PLAN_LAUNCH(rxr_scan_totals_kernel, dim3(1), t, 0, st, p, s, nb);
+    PLAN_LAUNCH(rxr_place_kernel, g, t, 0, st, p, s);
+    PLAN_LAUNCH(rxr_finish_kernel, g, t, 0, st, p, s);
+    return hipSuccess;
 }
 
 // classify, insert, link; decide; the scan of the totals, place, finish

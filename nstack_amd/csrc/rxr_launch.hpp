@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_prims.hpp"
 #include "rxr_plan.hpp"
 
 namespace rxr {
@@ -64,17 +65,13 @@ struct Scratch {
 };
 
 constexpr int kThreads = 512;       // rxr_kernel: 8 waves per CU, a quarter-wave per frame
-constexpr int kPlanThreads = 256;   // the plan kernels: one frame per thread
+using plan::kPlanThreads;           // the plan kernels: one frame per thread
+using plan::plan_blocks;
+using plan::table_size;
 
-inline uint64_t table_size(uint64_t n) {
-    uint64_t t = 16;
-    while (t < 2 * n) t <<= 1;
-    return t;
-}
-inline uint64_t plan_blocks(uint64_t n) { return (n + kPlanThreads - 1) / kPlanThreads; }
 // Bytes of scratch, and the carving of one allocation of that size (16-byte aligned parts).
 inline uint64_t scratch_bytes(uint64_t n) {
-    return n * (sizeof(Rec) + sizeof(Acc)) + table_size(n) * sizeof(Entry) + ((n * 4 + 15) & ~15ull) + plan_blocks(n) * 16;
+    return n * (sizeof(Rec) + sizeof(Acc)) + table_size(n) * sizeof(Entry) + plan::up16(n * 4) + plan_blocks(n) * 16;
 }
 inline Scratch carve(void *mem, uint64_t n) {
     Scratch s;
@@ -87,7 +84,7 @@ inline Scratch carve(void *mem, uint64_t n) {
     s.rec = reinterpret_cast<Rec *>(p);
     p += n * sizeof(Rec);
     s.headof = reinterpret_cast<uint32_t *>(p);
-    p += (n * 4 + 15) & ~15ull;
+    p += plan::up16(n * 4);
     s.totc = reinterpret_cast<uint64_t *>(p);
     s.totb = s.totc + plan_blocks(n);
     return s;

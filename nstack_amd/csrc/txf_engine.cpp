@@ -273,14 +273,9 @@ int plan_dev(bool tso, const uint16_t *mss, const void *dgram, uint64_t dgram_by
     p.flags = flags;
     p.mss = mss;
     // the block totals: scratch that lives on the stream, between the three launches
-    const uint64_t nb = (n + txf::kPlanThreads - 1) / txf::kPlanThreads;
-    uint64_t *tot = nullptr;
-    HIPTRY(hipMallocAsync((void **)&tot, nb * 8, st), "hipMallocAsync(block totals)");
-    const hipError_t e = tso ? txf::launch_plan_tso(p, status, first, tot, st) : txf::launch_plan(p, status, first, tot, st);
-    const hipError_t e2 = hipFreeAsync(tot, st);
-    HIPTRY(e, "launching the txf plan kernels");
-    HIPTRY(e2, "hipFreeAsync(block totals)");
-    return 0;
+    return with_stream_scratch(plan::plan_blocks(n) * 8, st, [&](void *mem) {
+        return (tso ? txf::launch_plan_tso : txf::launch_plan)(p, status, first, (uint64_t *)mem, st);
+    });
 }
 
 }  // namespace

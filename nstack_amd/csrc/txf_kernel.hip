@@ -49,6 +49,7 @@
 #include "fcs_crc.hpp"
 #include "fcs_tables.hpp"
 #include "frame_walk.hpp"
+#include "row_work.hpp"
 #include "txf_launch.hpp"
 
 namespace txf {
@@ -58,17 +59,15 @@ using fcs::kChunkWords;
 using fcs::kGroup;
 using fcs::kSegBytes;
 using fcs::u32x4a4;
+using row::gstore;
+using row::kRun;
+static_assert(fcs::kGroup == row::kGroup, "a quarter-wave per datagram");
 using rxv::fold64;
 using rxv::keep_range;
 using rxv::row_get;
 using rxv::row_sum;
 using rxv::swap16;
 using rxv::xor_field;
-
-template <typename T>
-__device__ __forceinline__ void gstore(uint64_t addr, T v) {
-    *reinterpret_cast<__attribute__((address_space(1))) T *>(addr) = v;
-}
 
 // What the L4 variant (include/nstack_txd.h) keeps besides; empty for the plain framer, whose
 // structures and code stay what they were.
@@ -147,8 +146,6 @@ struct Pos : PosL4<l4_of(M)> {
     Frame<M> fr;
 };
 
-constexpr uint64_t kRun = 8;   // datagrams a row takes from the work counter at a time
-
 struct Chunk {
     u32x4a4 x[6];
     uint32_t x6;
@@ -218,21 +215,7 @@ __device__ __forceinline__ void frame_walk(FParams p) {
     uint32_t tb0, tb1;
     fcs::table_bases(lane, tb0, tb1);
     const uint32_t lanebase = fcs::kLdsLane | ((uint32_t)(lane & 31) * 4u);
-    // this row's run of datagrams [cur, end), taken from p.ctr
-    uint64_t cur = 0, end = 0;
-    auto take = [&](bool want) {   // wave-uniform call: every row with `want` gets the next run
-        const uint64_t m = __ballot(want && j == 0);
-        if (m == 0) return;
-        const int leader = __ffsll((unsigned long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(p.ctr, (unsigned long long)__popcll(m) * kRun);
-        base = __shfl(base, leader, 64);
-        const uint64_t before = m & ((1ull << (lane & ~(kGroup - 1))) - 1ull);   // wanting rows in front of this one
-        if (want) {
-            cur = base + (uint64_t)__popcll(before) * kRun;
-            end = cur + kRun < p.n ? cur + kRun : p.n;
-        }
-    };
+    row::Run run;   // this row's run of datagrams, taken from p.ctr
 
     auto frame_of = [&](const Dg &g, uint32_t jf) -> Frame {
         Frame f;
@@ -401,16 +384,16 @@ __device__ __forceinline__ void frame_walk(FParams p) {
     // The row's next datagram that becomes frames; rows with `go` only.
     auto advance = [&](Pos &n, bool go) {
         while (__any(go)) {
-            take(go && cur >= end);
+            run.take(go && run.cur >= run.end, p.ctr, p.n);
             if (go) {
-                if (cur >= p.n) {
+                if (run.cur >= p.n) {
                     n.act = false;
                     if constexpr (L4) n.pre = false;
                     n.k = 0;
                     n.fr = idle_frame<M>();
                     go = false;
                 } else {
-                    const Dg g = load_dg(cur++);
+                    const Dg g = load_dg(run.cur++);
                     if (g.cnt) {
                         n.g = g;
                         n.jf = 0;
@@ -653,19 +636,6 @@ __global__ __launch_bounds__(NT, 1) void tso_kernel(FParams p) {
 // ---------------------------------------------------------------------------------------------
 // The plan: status words and the exclusive prefix sums of the frame counts.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kPlanThreads; o <<= 1) {
-        const uint64_t add = t >= o ? sh[t - o] : 0ull;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    return sh[t];
-}
-
 // first[i] = the frame count of datagram i; tot[block] = the block's sum.
 __global__ __launch_bounds__(kPlanThreads) void txf_plan_kernel(FParams p, uint32_t *status, uint64_t *first,
                                                                 uint64_t *tot) {
@@ -689,8 +659,9 @@ __global__ __launch_bounds__(kPlanThreads) void txf_plan_kernel(FParams p, uint3
         first[i] = o.cnt;
         cnt = o.cnt;
     }
-    const uint64_t incl = block_scan_incl(cnt, sh);
-    if (threadIdx.x == kPlanThreads - 1) tot[blockIdx.x] = incl;
+    uint64_t total;
+    plan::block_scan_incl(cnt, sh, total);
+    if (threadIdx.x == 0) tot[blockIdx.x] = total;
 }
 
 // The same for include/nstack_tso.h: header bytes 0..9 and, for candidates (tso_plan.hpp), segment
@@ -724,22 +695,15 @@ __global__ __launch_bounds__(kPlanThreads) void tso_plan_kernel(FParams p, uint3
         first[i] = t.o.cnt;
         cnt = t.o.cnt;
     }
-    const uint64_t incl = block_scan_incl(cnt, sh);
-    if (threadIdx.x == kPlanThreads - 1) tot[blockIdx.x] = incl;
+    uint64_t total;
+    plan::block_scan_incl(cnt, sh, total);
+    if (threadIdx.x == 0) tot[blockIdx.x] = total;
 }
 
 // One workgroup: tot[b] becomes the sum of the blocks in front of b; *total the sum of all.
 __global__ __launch_bounds__(kPlanThreads) void txf_scan_totals_kernel(uint64_t *tot, uint64_t nb, uint64_t *total) {
     __shared__ uint64_t sh[kPlanThreads];
-    uint64_t base = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += kPlanThreads) {
-        const uint64_t b = b0 + threadIdx.x;
-        const uint64_t v = b < nb ? tot[b] : 0ull;
-        const uint64_t incl = block_scan_incl(v, sh);
-        if (b < nb) tot[b] = base + incl - v;
-        base += sh[kPlanThreads - 1];
-        __syncthreads();
-    }
+    const uint64_t base = plan::scan_totals(tot, nb, sh);
     if (threadIdx.x == 0) *total = base;
 }
 
@@ -748,8 +712,8 @@ __global__ __launch_bounds__(kPlanThreads) void txf_add_kernel(uint64_t *first, 
     __shared__ uint64_t sh[kPlanThreads];
     const uint64_t i = (uint64_t)blockIdx.x * kPlanThreads + threadIdx.x;
     const uint64_t v = i < n ? first[i] : 0ull;
-    const uint64_t incl = block_scan_incl(v, sh);
-    if (i < n) first[i] = tot[blockIdx.x] + incl - v;
+    const uint64_t excl = plan::block_scan_excl(v, sh);
+    if (i < n) first[i] = tot[blockIdx.x] + excl;
 }
 
 namespace {
@@ -784,15 +748,12 @@ template <class K>
 hipError_t launch_plan_with(K count_kernel, const FParams &p, uint32_t *status, uint64_t *first, uint64_t *tot, hipStream_t st) {
     (void)hipGetLastError();
     if (!p.n) return hipSuccess;
-    const uint64_t nb = (p.n + kPlanThreads - 1) / kPlanThreads;
+    const uint64_t nb = plan::plan_blocks(p.n);
     if (nb > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(count_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p, status, first, tot);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(txf_scan_totals_kernel, dim3(1), dim3(kPlanThreads), 0, st, tot, nb, first + p.n);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(txf_add_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, first, (const uint64_t *)tot, p.n);
-    return hipGetLastError();
+    PLAN_LAUNCH(count_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, p, status, first, tot);
+    PLAN_LAUNCH(txf_scan_totals_kernel, dim3(1), dim3(kPlanThreads), 0, st, tot, nb, first + p.n);
+    PLAN_LAUNCH(txf_add_kernel, dim3((unsigned)nb), dim3(kPlanThreads), 0, st, first, (const uint64_t *)tot, p.n);
+    return hipSuccess;
 }
 }  // namespace
 

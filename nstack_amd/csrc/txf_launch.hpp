@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_prims.hpp"
 #include "tso_plan.hpp"
 #include "txf_plan.hpp"
 
@@ -32,7 +33,7 @@ struct FParams {
 enum class Mode { kPlain, kL4, kTso };
 
 constexpr int kThreads = 512;       // txf_kernel: 8 waves per CU, a quarter-wave per datagram
-constexpr int kPlanThreads = 256;   // the plan kernels: one datagram per thread
+using plan::kPlanThreads;           // the plan kernels: one datagram per thread
 
 enum class Route { kNone, kGeneral, kGeneralFcs, kGeneralL4, kGeneralL4Fcs, kTso, kTsoFcs };
 Route last_launch();      // what the last launch_txf of Mode::kPlain of this process launched (tests)

@@ -373,3 +373,36 @@ def test_host_counters_stay_untouched(dev, oracle, inet_oracle):
     b = TBatch(oracle, inet_oracle, [tcp_datagram(rng, 20, 20, 5000), l4_datagram(rng, 17, 24, 100)], 1500, FCS, seed=79)
     b.check(dev)
     assert (L.fcs_engine_host_batches(), L.fcs_engine_host_fallbacks()) == before
+
+
+# ---- 14. the plan's scan at the block borders and past one pass of the totals scan ----
+@pytest.mark.parametrize("n", [255, 256, 257, 65537])
+def test_plan_prefix_sums(dev, inet_oracle, n):
+    """n tiny TCP datagrams of a few kinds (segmented into 2..8 frames, whole, SYN, UDP, refused) at every
+    alignment: first[] and status[] of ip_tx_tso_plan_dev against tso_model, one model call per kind."""
+    rng = np.random.default_rng(700 + n)
+    kinds = [(tcp_datagram(rng, 20, 20, P, ALL), m) for P, m in ((2, 1), (8, 1), (7, 3), (5, 2), (8, 3), (4, 4), (0, 1))]
+    kinds += [(tcp_datagram(rng, 24, 24, 6, tm.ACK), 2), (tcp_datagram(rng, 20, 20, 6, tm.SYN), 1),
+              (l4_datagram(rng, 17, 20, 9), 1), (bytes(7), 1)]
+    k_st, k_first = tm.plan_status(inet_oracle, [d for d, _ in kinds], 1500, 0, [m for _, m in kinds])
+    k_cnt = np.diff(k_first)
+    assert sorted(set(int(c) for c in k_cnt)) == [0, 1, 2, 3, 8] and (k_st & tm.SEGMENTED).any() and (k_st & fm.BAD_HDR).any()
+    pick = rng.integers(0, len(kinds), n)
+    ln = np.array([len(d) for d, _ in kinds], dtype=np.uint32)[pick]
+    end = np.cumsum(ln.astype(np.uint64) + rng.integers(0, 4, n).astype(np.uint64))   # gaps of 0..3: every alignment
+    off = (end - ln).astype(np.uint64)
+    arena = np.zeros(int(end[-1]) + 8, dtype=np.uint8)
+    for k, (d, _) in enumerate(kinds):
+        at = off[pick == k]
+        arena[(at[:, None] + np.arange(len(d), dtype=np.uint64)).astype(np.int64)] = np.frombuffer(d, dtype=np.uint8)
+    mss = np.array([m for _, m in kinds], dtype=np.uint16)[pick]
+    want = np.zeros(n + 1, dtype=np.uint64)
+    want[1:] = np.cumsum(k_cnt[pick])
+    d_arena = to_dev(arena, dev)
+    d_first = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+    d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    na.tx_tso_plan_dev(d_arena, arena.size, to_dev(off, dev), to_dev(ln, dev), to_dev(mss.view(np.int16), dev), n, 1500,
+                       d_first, 0, d_st)
+    torch.cuda.synchronize()
+    assert (d_first.cpu().numpy().view(np.uint64) == want).all()
+    assert (d_st.cpu().numpy().view(np.uint32) == k_st[pick]).all()
