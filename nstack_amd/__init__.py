@@ -44,7 +44,12 @@ __all__ = ["FcsError", "lib", "load", "ether_fcs", "fixed_dev", "batch_dev", "fi
            "rx_demux_plan_host", "rx_demux_plan_dev", "rx_demux_dev", "rx_demux_host", "dmx_last_launch",
            "dmx_last_host_chunks", "dmx_key", "DMX_EXPORTS", "DMX_DROPPED", "DMX_NO_PROTO", "DMX_SHORT", "DMX_CTRL",
            "DMX_NO_SOCK", "DMX_QUEUED", "DMX_NO_ROOM", "DMX_DELIVERED", "DMX_NONE32", "DMX_NONE64", "DMX_MAX_SOCKS",
-           "DMX_REC_HDR", "DMX_SCRATCH_PER_N", "DMX_SCRATCH_PER_S", "DMX_SCRATCH_FIXED"]
+           "DMX_REC_HDR", "DMX_SCRATCH_PER_N", "DMX_SCRATCH_PER_S", "DMX_SCRATCH_FIXED",
+           "tx_mux_plan_host", "tx_mux_plan_dev", "tx_mux_dev", "tx_mux_host", "mux_last_launch", "mux_last_host_chunks",
+           "MUX_EXPORTS", "MUX_BAD_REC", "MUX_BAD_SIZE", "MUX_NO_TCB", "MUX_NO_ROUTE", "MUX_NO_NEIGH", "MUX_PLANNED",
+           "MUX_NO_ROOM", "MUX_BUILT", "MUX_MAX_SOCKS", "MUX_MAX_ROUTES", "MUX_MAX_NEIGH", "MUX_REC_HDR", "MUX_IMG",
+           "MUX_UDP_MAX", "MUX_TCP_MAX", "MUX_SCRATCH_PER_N", "MUX_SCRATCH_PER_S", "MUX_SCRATCH_PER_NB", "MUX_SCRATCH_FIXED",
+           "MUX_TCB_DTYPE", "MUX_ROUTE_DTYPE", "MUX_NEIGH_DTYPE"]
 
 # Every symbol include/nstack_fcs.h declares (tests check the .so exports all of them).
 EXPORTS = [
@@ -132,6 +137,19 @@ DMX_NO_SOCK, DMX_QUEUED, DMX_NO_ROOM, DMX_DELIVERED = 0x010, 0x020, 0x040, 0x080
 DMX_NONE32, DMX_NONE64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 DMX_MAX_SOCKS, DMX_REC_HDR = 65536, 24
 DMX_SCRATCH_PER_N, DMX_SCRATCH_PER_S, DMX_SCRATCH_FIXED = 26, 48, 4096
+
+# include/nstack_mux.h — one-pass TX multiplexing (its own list, as DMX_EXPORTS)
+MUX_EXPORTS = ["ip_tx_mux_plan_host", "ip_tx_mux_plan_dev", "ip_tx_mux_dev", "ip_tx_mux_host",
+               "fcs_debug_mux_last_launch", "fcs_debug_mux_last_host_chunks"]
+MUX_BAD_REC, MUX_BAD_SIZE, MUX_NO_TCB, MUX_NO_ROUTE = 0x001, 0x002, 0x004, 0x008
+MUX_NO_NEIGH, MUX_PLANNED, MUX_NO_ROOM, MUX_BUILT = 0x010, 0x020, 0x040, 0x080
+MUX_MAX_SOCKS, MUX_MAX_ROUTES, MUX_MAX_NEIGH, MUX_REC_HDR, MUX_IMG = 65536, 256, 65536, 24, 40
+MUX_UDP_MAX, MUX_TCP_MAX = 65506, 65495
+MUX_SCRATCH_PER_N, MUX_SCRATCH_PER_S, MUX_SCRATCH_PER_NB, MUX_SCRATCH_FIXED = 25, 0, 48, 1024
+# numpy layouts of struct mux_tcb, mux_route and mux_neigh (12, 24 and 12 bytes)
+MUX_TCB_DTYPE = [("seq", "<u4"), ("ack", "<u4"), ("win", "<u2"), ("flags", "u1"), ("pad", "u1")]
+MUX_ROUTE_DTYPE = [("network", "<u4"), ("netmask", "<u4"), ("gw", "<u4"), ("iface", "<u4"), ("mac", "u1", (6,)), ("pad", "<u2")]
+MUX_NEIGH_DTYPE = [("addr", "<u4"), ("mac", "u1", (6,)), ("valid", "<u2")]
 
 # include/nstack_inet.h modes: the reference function each result reproduces
 INET_CSUM_IP, INET_CSUM_TCP, INET_CSUM_UDP = 0, 1, 2
@@ -308,6 +326,13 @@ def _bind(path: str) -> ctypes.CDLL:
         "ip_rx_demux_host": (c.c_int64, [vp, u64, vp, vp, vp, u64, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
         "fcs_debug_dmx_last_launch": (i32, [c.c_char_p, u64]),
         "fcs_debug_dmx_last_host_chunks": (c.c_int64, [vp, u64]),
+        "ip_tx_mux_plan_host": (c.c_int64, [vp, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "ip_tx_mux_plan_dev": (i32, [vp, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ip_tx_mux_dev": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, vp, u64, vp, vp]),
+        "ip_tx_mux_host": (c.c_int64, [vp, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp,
+                                       vp, vp]),
+        "fcs_debug_mux_last_launch": (i32, [c.c_char_p, u64]),
+        "fcs_debug_mux_last_host_chunks": (c.c_int64, [vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1155,4 +1180,63 @@ def dmx_last_host_chunks() -> list:
     k = _check(load().fcs_debug_dmx_last_host_chunks(None, 0), "fcs_debug_dmx_last_host_chunks")
     buf = (ctypes.c_uint64 * max(k, 1))()
     load().fcs_debug_dmx_last_host_chunks(buf, k)
+    return list(buf[:k])
+
+
+# ---- one-pass TX multiplexing (include/nstack_mux.h) ----
+def tx_mux_plan_host(q, q_bytes: int, rec, n: int, sfirst, bind, nsock: int, tcb, rt, nrt: int, nb, nnb: int, mstat, off, ln, l2,
+                     himg, tnext=None, counts=None, id0: int = 0, align: int = 16) -> int:
+    """The plan of n send records (socket-major: sfirst[nsock + 1], bind[nsock] dmx_key keys, tcb[nsock]
+    or None) against rt[nrt] and nb[nnb]: mstat, off, ln, l2 (12 bytes) and himg (40 bytes) per record,
+    tnext[nsock], counts[4] = {planned, bytes, no route, no neighbour} (u64). Host arithmetic, no GPU.
+    Returns the planned count; counts[1] sizes dgram."""
+    return _check(load().ip_tx_mux_plan_host(_ptr(q), q_bytes, _ptr(rec), n, _ptr(sfirst), _ptr(bind), _u32(nsock, "nsock"),
+                                             _ptr(tcb), _ptr(rt), _u32(nrt, "nrt"), _ptr(nb), _u32(nnb, "nnb"), _u32(id0, "id0"),
+                                             _u32(align, "align"), _ptr(mstat), _ptr(off), _ptr(ln), _ptr(l2), _ptr(himg),
+                                             _ptr(tnext), _ptr(counts)),
+                  "ip_tx_mux_plan_host")
+
+
+def tx_mux_plan_dev(q, q_bytes: int, rec, n: int, sfirst, bind, nsock: int, tcb, rt, nrt: int, nb, nnb: int, mstat, off, ln, l2,
+                    himg, tnext, counts, id0: int = 0, align: int = 16, stream=None) -> None:
+    """The same arrays in device memory (the tables too); asynchronous on `stream`."""
+    _check(load().ip_tx_mux_plan_dev(_ptr(q), q_bytes, _ptr(rec), n, _ptr(sfirst), _ptr(bind), _u32(nsock, "nsock"), _ptr(tcb),
+                                     _ptr(rt), _u32(nrt, "nrt"), _ptr(nb), _u32(nnb, "nnb"), _u32(id0, "id0"),
+                                     _u32(align, "align"), _ptr(mstat), _ptr(off), _ptr(ln), _ptr(l2), _ptr(himg), _ptr(tnext),
+                                     _ptr(counts), _stream(stream)),
+           "ip_tx_mux_plan_dev")
+
+
+def tx_mux_dev(q, q_bytes: int, rec, n: int, pstat, off, ln, himg, dgram, dgram_bytes: int, align: int = 16, mstat=None,
+               stream=None) -> None:
+    """Writes the datagrams of the plan into dgram (aligned to `align`); mstat gets the final words
+    (MUX_BUILT / MUX_NO_ROOM). Device arrays; asynchronous on `stream`."""
+    _check(load().ip_tx_mux_dev(_ptr(q), q_bytes, _ptr(rec), n, _ptr(pstat), _ptr(off), _ptr(ln), _ptr(himg), _u32(align, "align"),
+                                _ptr(dgram), dgram_bytes, _ptr(mstat), _stream(stream)),
+           "ip_tx_mux_dev")
+
+
+def tx_mux_host(q, q_bytes: int, rec, n: int, sfirst, bind, nsock: int, tcb, rt, nrt: int, nb, nnb: int, dgram, dgram_bytes: int,
+                id0: int = 0, align: int = 16, mstat=None, off=None, ln=None, l2=None, himg=None, tnext=None, counts=None) -> int:
+    """Host form: host memory in and out, built on the GPU in pipeline chunks. Returns the planned
+    count; mux_last_host_chunks() reports its chunks."""
+    return _check(load().ip_tx_mux_host(_ptr(q), q_bytes, _ptr(rec), n, _ptr(sfirst), _ptr(bind), _u32(nsock, "nsock"), _ptr(tcb),
+                                        _ptr(rt), _u32(nrt, "nrt"), _ptr(nb), _u32(nnb, "nnb"), _u32(id0, "id0"),
+                                        _u32(align, "align"), _ptr(dgram), dgram_bytes, _ptr(mstat), _ptr(off), _ptr(ln), _ptr(l2),
+                                        _ptr(himg), _ptr(tnext), _ptr(counts)),
+                  "ip_tx_mux_host")
+
+
+def mux_last_launch() -> str:
+    """The kernel the last multiplexing build launch of this process launched."""
+    buf = ctypes.create_string_buffer(32)
+    _check(load().fcs_debug_mux_last_launch(buf, 32), "fcs_debug_mux_last_launch")
+    return buf.value.decode()
+
+
+def mux_last_host_chunks() -> list:
+    """The records of each chunk the calling thread's last tx_mux_host cut its batch into."""
+    k = _check(load().fcs_debug_mux_last_host_chunks(None, 0), "fcs_debug_mux_last_host_chunks")
+    buf = (ctypes.c_uint64 * max(k, 1))()
+    load().fcs_debug_mux_last_host_chunks(buf, k)
     return list(buf[:k])
